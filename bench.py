@@ -31,8 +31,16 @@ no collective, and only the per-second MetricNode all-gather (RCCL) inside the t
 chunk barriers synchronise them.  The step time is the max over ranks and value = every rank's
 entries / that time.
 
-After the C4 line's measurement (N = 1), the same pipeline measures the other SURVEY.md §8(d) configs
-C2, C3, C5 and C6 (bounded traces, inputs in HBM) and reports them under "configs" (--no-configs: skip).
+A plain run (bench.py --gpus 1 --steps K --warmup W) does only what the headline needs: set-up, warm-up, the K
+timed steps, the result line.  --dump-outputs DIR then writes what the last timed step's last batch returned to
+its caller (dump_outputs below), so that two builds can be compared output for output: the inputs are seeded and
+the same from run to run.
+
+--full adds everything else the benchmark measures, each in runs of its own after the timed steps (N = 1): the
+device-to-device stream copy rate (the second roofline denominator), the oracle's CPU baseline on a prefix of the
+same trace (--no-cpu-baseline: skip), and the other SURVEY.md §8(d) configs C2, C3, C5 and C6 (bounded traces,
+inputs in HBM) with the drop-in, latency and token-server lines, reported under "configs" (--no-configs: skip).
+Without --full those fields of the result line are null.
 """
 from __future__ import annotations
 
@@ -41,6 +49,7 @@ import hashlib
 import json
 import os
 import sys
+import threading
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -71,7 +80,13 @@ def parse():
                    help="fraction of free HBM for one timed chunk's inputs")
     p.add_argument("--sharding", choices=("balanced", "hash"), default="balanced",
                    help="resource -> GPU partition: balanced by event counts, or splitmix64(res_id) %% N")
-    p.add_argument("--no-configs", action="store_true", help="skip the C2 / C3 / C5 / C6 sub-lines")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure the stream copy rate, the CPU baseline and the other "
+                        "configs' sub-lines (off: those fields of the result line are null)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed batch returned (its decisions, and the "
+                        "node state they left) as DIR/<name>.npy, float64")
+    p.add_argument("--no-configs", action="store_true", help="--full: skip the C2 / C3 / C5 / C6 sub-lines")
     p.add_argument("--only-config", default="", metavar="C2|C3|C5|C5-ext|C6",
                    help="measure only that config sub-line (no headline; tools/pmc_configs.py profiles it)")
     p.add_argument("--resources", type=int, default=1_000_000)
@@ -79,7 +94,7 @@ def parse():
                    help="partitioned oracle threads (0: this job's CPU share -- cgroup cpu.max, else min(16, cores))")
     p.add_argument("--cpu-sample-events", type=int, default=24_000_000)
     p.add_argument("--cpu-single-events", type=int, default=6_000_000)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle's CPU baselines")
     p.add_argument("--balance-alpha", type=float, default=0.9,
                    help="--sharding balanced: a resource's load = its history-window events ** alpha")
     p.add_argument("--rank-batches", default="auto",
@@ -162,6 +177,41 @@ def shifted_batch(base64, a: int, e: int, copy: int, tspan: int, n_base: int, ou
         out64[:, 2] += torch.where(isref, copy * n_base, 0)
 
 
+DUMP_SAMPLE = 1 << 21   # decisions written by --dump-outputs (16 MB as float64), a seeded sample of a larger batch
+DUMP_NODES = 256        # resources whose node state is written: the first distinct ones of the trace + a seeded sample
+DUMP_SEED = 20240601
+
+
+def dump_outputs(dirname: str, eng, out, m: int, ev, n_res: int, suffix: str = ""):
+    """--dump-outputs: what the caller of the timed path holds after the last timed step, as float64 .npy files.
+
+    decisions.npy  the decision words (status | rule_slot << 8 | wait_ms << 16) the last timed batch wrote for its m
+                   events; of a batch above DUMP_SAMPLE events, those at DUMP_SAMPLE seeded positions (sorted, the
+                   same for every run with the same m)
+    node_second.npy, node_minute.npy  sg_read_node's second [8, 8] and minute [60, 8] windows of 2 x DUMP_NODES
+                   resources after that batch (every timed and warm-up batch has gone into them): the first
+                   DUMP_NODES distinct resources of the trace and DUMP_NODES seeded ones
+    Every value is an integer below 2^53, so float64 holds it exactly."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    dec = out[:m]
+    if m > DUMP_SAMPLE:
+        idx = np.sort(rng.integers(0, m, DUMP_SAMPLE))
+        dec = dec[torch.from_numpy(idx).to(out.device)]
+    # the words are uint32 in an int32 tensor
+    np.save(os.path.join(dirname, "decisions%s.npy" % suffix),
+            dec.cpu().numpy().view(np.uint32).astype(np.float64))
+    head = ev["res_id"][:1 << 16]
+    _, first = np.unique(head, return_index=True)
+    ids = np.concatenate([head[np.sort(first)][:DUMP_NODES].astype(np.int64),
+                          np.sort(rng.choice(n_res, min(DUMP_NODES, n_res), replace=False))])
+    nodes = [eng.read_node(int(r)) for r in ids]
+    for k in ("second", "minute"):
+        np.save(os.path.join(dirname, "node_%s%s.npy" % (k, suffix)),
+                np.stack([n[k] for n in nodes]).astype(np.float64))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.shard:
@@ -181,6 +231,27 @@ def main():
     if not args.shard and world != args.gpus:
         sys.exit("bench.py: --gpus %d but WORLD_SIZE=%d: launch one process per GPU (torchrun "
                  "--nproc-per-node %d, or bench.py --gpus %d alone)" % (args.gpus, world, args.gpus, args.gpus))
+    shard = tuple(int(x) for x in args.shard.split("/")) if args.shard else None  # (R, N)
+    if shard:
+        assert world == 1 and 0 <= shard[0] < shard[1], "--shard R/N: one process, 0 <= R < N"
+    nparts = shard[1] if shard else world
+    me = shard[0] if shard else rank
+    steps, warmup, gb, B = args.steps, args.warmup, args.batch_events, args.base_batches
+    S = max(1, args.sub_batches)
+    # ---- one trace for the whole node, generated (a C call of ~10 s on one thread) while this thread imports torch
+    # and, on one GPU, creates and loads the engine
+    from sentinel_amd import tracegen as T
+    gen = {}
+
+    def generate():
+        t_gen = time.time()
+        try:
+            gen["trace"] = make_trace(args.resources, gb, B, T.SEED_BASE + 4)
+        except BaseException as e:  # raised again in the main thread
+            gen["error"] = e
+        gen["s"] = time.time() - t_gen
+    gen_thread = threading.Thread(target=generate)
+    gen_thread.start()
     import torch
     # SG_BENCH_GLOO=1 rehearses the multi-rank path on a one-GPU box: gloo instead of RCCL, every rank on
     # device local % device_count (never used for a reported number)
@@ -199,20 +270,25 @@ def main():
 
     from sentinel_amd import dist as D
     from sentinel_amd import engine as E
-    from sentinel_amd import tracegen as T
 
-    steps, warmup, gb, B = args.steps, args.warmup, args.batch_events, args.base_batches
-    S = max(1, args.sub_batches)
-    # ---- one trace for the whole node; this rank's shard of it
-    t_gen = time.time()
-    w, ev = make_trace(args.resources, gb, B, T.SEED_BASE + 4)
-    gen_s = time.time() - t_gen
+    def make_engine(max_batch_events, wl):
+        e = E.Engine(device=dev.index, max_resources=1 << 20, max_slot_chain_size=0, param_table_log2=16,
+                     status_ring_log2=28, max_batch_events=max_batch_events)
+        wl.install(e)
+        return e
+
+    eng = rules_w = None
+    if nparts == 1:
+        # names and rules are a function of (config, seed, resources) alone (csrc/tracegen.cpp gen_zipf draws them before
+        # the first event), so a one-entry workload holds the trace's; every batch of the whole trace has gb events
+        rules_w = T.Workload(4, seed=T.SEED_BASE + 4, n_res=args.resources, n_entries=1)
+        eng = make_engine(gb, rules_w)
+    gen_thread.join()
+    if "error" in gen:
+        raise gen["error"]
+    (w, ev), gen_s = gen["trace"], gen["s"]
+    # ---- this rank's shard of the trace
     tspan = int(ev["ts"][-1] - ev["ts"][0]) + 1000  # copy k starts a second after copy k-1 ends
-    shard = tuple(int(x) for x in args.shard.split("/")) if args.shard else None  # (R, N)
-    if shard:
-        assert world == 1 and 0 <= shard[0] < shard[1], "--shard R/N: one process, 0 <= R < N"
-    nparts = shard[1] if shard else world
-    me = shard[0] if shard else rank
     table = None
     if nparts > 1:
         # every rank computes the same table from the same history window: the event counts of the first
@@ -230,12 +306,12 @@ def main():
     LB, per_step, cuts = rank_batch_cuts(pos if nparts > 1 else None, n_base, gb, B, S, nparts, kb)
     sizes = np.diff(cuts)
     ent_b = np.array([int((mine["kind"][cuts[b]:cuts[b + 1]] == 0).sum()) for b in range(LB)])
-    res_b = np.array([len(np.unique(mine["res_id"][cuts[b]:cuts[b + 1]])) for b in range(LB)])
+    res_b = np.array([int(np.count_nonzero(np.bincount(mine["res_id"][cuts[b]:cuts[b + 1]]))) for b in range(LB)])
     end_b = np.array([int(mine["ts"][max(cuts[b], cuts[b + 1] - 1)]) for b in range(LB)])
 
-    eng = E.Engine(device=dev.index, max_resources=1 << 20, max_slot_chain_size=0, param_table_log2=16,
-                   status_ring_log2=28, max_batch_events=int(sizes.max()))
-    w.install(eng)
+    if eng is None:
+        eng = make_engine(int(sizes.max()), w)
+    assert nparts > 1 or int(sizes.max()) == gb
 
     # ---- the shard's base batches into HBM (pinned host -> device; the PCIe rate is reported, never value)
     host = torch.from_numpy(np.ascontiguousarray(mine).view(np.uint8)).pin_memory()
@@ -338,6 +414,9 @@ def main():
     if dist is not None and n_gather == 0:  # at least one all-gather per run, untimed
         rows_gathered += gather_metrics(plan[-1][4])
         n_untimed = 1
+    if args.dump_outputs:  # the last timed batch's decisions are still in out
+        dump_outputs(args.dump_outputs, eng, out, plan[-1][1], mine, args.resources,
+                     "_rank%d" % rank if world > 1 else "")
     stage_ms = np.array(stage_rows)
     if dist is not None:
         t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
@@ -378,12 +457,13 @@ def main():
                    "measured on one GPU, this run has %d ranks" % world if world > 1 else
                    "measured on the whole trace, this run is one shard")
             tnote = "profiles/pmc_latest.json is for other sources/config (%s): not used" % why
-    stream = stream_copy_gbps(dev) if rank == 0 else None
+    # ---- --full only: measurements that take runs of their own
+    stream = stream_copy_gbps(dev) if args.full and rank == 0 else None
     cpu = None
-    if rank == 0 and world == 1 and not shard and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not shard and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, ev, args)
     configs = None
-    if rank == 0 and world == 1 and not shard and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and not shard and not args.no_configs:
         del buf, base, base64, out
         eng.close()
         torch.cuda.empty_cache()
@@ -398,6 +478,7 @@ def main():
             "steps": steps,
             "warmup": warmup,
             "ms_per_step": elapsed / steps * 1e3,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "strong",   # one trace partitioned over the ranks: total work is fixed as N grows
             "vs_baseline": None,
