@@ -384,6 +384,34 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
 int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs, uint64_t n, const uint64_t* values,
                                     uint64_t n_values, sg_token_result* out);
 
+/* Namespaces of the token server (csrv/flow/statistic/limit/GlobalRequestLimiter.java:30-80,
+ * csrv/flow/rule/ClusterFlowRuleManager.java:308-317): every namespace has a RequestLimiter of its own and a
+ * connected-client count of its own, and a token request tries the limiter of its flowId's namespace only
+ * (csrv/flow/ClusterFlowChecker.java:50-53, ClusterParamFlowChecker.java:37-40).  The namespace "default"
+ * (ServerConstants.DEFAULT_NAMESPACE) always exists with id 0 and the limit cfg.cluster_max_allowed_qps, and a
+ * flowId that was never assigned belongs to it: an engine on which none of these calls is made has one limiter. */
+#define SG_MAX_NAMESPACES 1024
+
+/* Register ns (idempotent; *out_ns_id, optional, receives its dense id), or change the limit of a registered
+ * namespace, which keeps its window (RequestLimiter.setQpsAllowed).  max_allowed_qps < 0: no limiter, every
+ * request passes it.  NULL or "": SG_EINVAL; more than SG_MAX_NAMESPACES namespaces: SG_ECAPACITY. */
+int sg_cluster_namespace(sg_engine* e, const char* ns, double max_allowed_qps, uint32_t* out_ns_id);
+
+/* flowIds of ns, for cluster flow rules and cluster param rules alike, loaded now or at any later load.
+ * Unregistered ns: SG_ENOTFOUND; a flow_id <= 0: SG_EINVAL; a flowId of another namespace: SG_ESTATE
+ * (nothing is assigned then; the same namespace again is a no-op). */
+int sg_cluster_assign_flows(sg_engine* e, const char* ns, const int64_t* flow_ids, uint32_t n);
+
+/* ConnectionManager.getConnectedCount(namespace): the count of every loaded flow of ns, and the count a flow
+ * of ns loaded later starts with.  A later per-flow call overrides it for that flow (the last call wins). */
+int sg_cluster_set_namespace_connected(sg_engine* e, const char* ns, int32_t connected);
+
+/* GlobalRequestLimiter.getCurrentQps / getMaxAllowedQps of ns (GlobalRequestLimiter.java:57-71): the sum of the
+ * limiter's buckets valid at now_ms over one second, and the limit (negative: none).  A read-back: no bucket
+ * is created or reset.  Either out pointer may be NULL. */
+int sg_cluster_namespace_qps(sg_engine* e, const char* ns, int64_t now_ms, double* current_qps,
+                             double* max_allowed_qps);
+
 /* Node read-back for parity tests: the ClusterNode of res_id. */
 int sg_read_node(sg_engine* e, uint32_t res_id, int64_t now_ms, sg_node_state* out);
 

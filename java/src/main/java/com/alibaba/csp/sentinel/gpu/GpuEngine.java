@@ -180,6 +180,61 @@ final class GpuEngine {
         }
     }
 
+    // ---- token server namespaces (GlobalRequestLimiter / ConnectionManager per namespace)
+    private interface NativeCall {
+        int run(Arena a) throws Throwable;
+    }
+
+    private void nativeCall(NativeCall c) {
+        synchronized (nativeLock) {
+            try (Arena a = Arena.ofConfined()) {
+                SentinelGpu.check(c.run(a));
+            } catch (RuntimeException ex) {
+                throw ex;
+            } catch (Throwable t) {
+                throw new IllegalStateException(t);
+            }
+        }
+    }
+
+    /** Register a namespace or change its maxAllowedQps (negative: no limiter); returns its dense id. */
+    int clusterNamespace(String ns, double maxAllowedQps) {
+        int[] id = new int[1];
+        nativeCall(a -> {
+            MemorySegment out = a.allocate(JAVA_INT);
+            int rc = (int)SentinelGpu.CLUSTER_NAMESPACE.invokeExact(handle, a.allocateFrom(ns), maxAllowedQps, out);
+            id[0] = out.get(JAVA_INT, 0);
+            return rc;
+        });
+        return id[0];
+    }
+
+    /** The flowIds (flow and param rules alike) of a registered namespace. */
+    void clusterAssignFlows(String ns, long[] flowIds) {
+        nativeCall(a -> (int)SentinelGpu.CLUSTER_ASSIGN_FLOWS.invokeExact(handle, a.allocateFrom(ns),
+            a.allocateFrom(JAVA_LONG, flowIds), flowIds.length));
+    }
+
+    /** ConnectionManager.getConnectedCount(namespace) of every flow of the namespace. */
+    void clusterSetNamespaceConnected(String ns, int connected) {
+        nativeCall(a -> (int)SentinelGpu.CLUSTER_SET_NAMESPACE_CONNECTED.invokeExact(handle, a.allocateFrom(ns),
+            connected));
+    }
+
+    /** {GlobalRequestLimiter.getCurrentQps(namespace) at now, getMaxAllowedQps(namespace)}. */
+    double[] clusterNamespaceQps(String ns, long now) {
+        double[] out = new double[2];
+        nativeCall(a -> {
+            MemorySegment cur = a.allocate(java.lang.foreign.ValueLayout.JAVA_DOUBLE);
+            MemorySegment lim = a.allocate(java.lang.foreign.ValueLayout.JAVA_DOUBLE);
+            int rc = (int)SentinelGpu.CLUSTER_NAMESPACE_QPS.invokeExact(handle, a.allocateFrom(ns), now, cur, lim);
+            out[0] = cur.get(java.lang.foreign.ValueLayout.JAVA_DOUBLE, 0);
+            out[1] = lim.get(java.lang.foreign.ValueLayout.JAVA_DOUBLE, 0);
+            return rc;
+        });
+        return out;
+    }
+
     // ---- events
     /** Enqueue an ENTRY and park until the batcher has its decision word. */
     int decide(Op op) {

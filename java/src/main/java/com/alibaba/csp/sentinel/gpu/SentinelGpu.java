@@ -214,7 +214,17 @@ final class SentinelGpu {
         rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));
     static final MethodHandle CLUSTER_REQUEST_PARAM_TOKENS = fn("sg_cluster_request_param_tokens",
         rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS));
-    static final MethodHandle READ_NODE = fn("sg_read_node", rc(ADDRESS, JAVA_INT, JAVA_LONG, ADDRESS));
+    /** Namespaces: (engine, ns, maxAllowedQps, int* id) / (engine, ns, long* flowIds, n) / (engine, ns, connected) /
+     *  (engine, ns, now, double* currentQps, double* maxAllowedQps). */
+    static final MethodHandle CLUSTER_NAMESPACE = fn("sg_cluster_namespace",
+        rc(ADDRESS, ADDRESS, JAVA_DOUBLE, ADDRESS));
+    static final MethodHandle CLUSTER_ASSIGN_FLOWS = fn("sg_cluster_assign_flows",
+        rc(ADDRESS, ADDRESS, ADDRESS, JAVA_INT));
+    static final MethodHandle CLUSTER_SET_NAMESPACE_CONNECTED = fn("sg_cluster_set_namespace_connected",
+        rc(ADDRESS, ADDRESS, JAVA_INT));
+    static final MethodHandle CLUSTER_NAMESPACE_QPS = fn("sg_cluster_namespace_qps",
+        rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS));
+    static final MethodHandle READ_NODE =fn("sg_read_node", rc(ADDRESS, JAVA_INT, JAVA_LONG, ADDRESS));
     /** ParameterMetric.getThreadCount(paramIdx, value): (engine, res, paramIdx, key, long* count, int* present). */
     static final MethodHandle PARAM_THREAD_COUNT =
         fn("sg_param_thread_count", rc(ADDRESS, JAVA_INT, JAVA_INT, JAVA_LONG, ADDRESS, ADDRESS));

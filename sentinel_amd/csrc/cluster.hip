@@ -13,7 +13,8 @@
 //   2. the namespace's GlobalRequestLimiter, in request order.  Inside one 100 ms bucket the set of valid
 //      buckets is fixed, so the passes of a bucket are a prefix of its candidates: k_lim_walk takes one
 //      step per bucket (their candidate counts from a scan), k_lim_apply ranks every request in its
-//      bucket (parallel);
+//      bucket (parallel).  With several namespaces (each its own limiter and limit) the candidates are first
+//      grouped by namespace and a wave per namespace walks its own buckets (2' below: k_nsl_*);
 //   3. stable radix sort of the limiter-passed requests by flow index (kernels.hip), then k_tok_flow_wg
 //      (a workgroup per flowId) runs acquireClusterToken over the flow's requests in time order against
 //      the flow's ClusterMetric, kept in HBM between batches.  Inside one window sub-bucket the valid
@@ -39,35 +40,43 @@ __device__ __forceinline__ uint64_t tab_hash(int64_t k) {
     return z ^ (z >> 31);
 }
 
-__device__ uint32_t tab_find(const CSlot* __restrict__ tab, uint32_t mask, int64_t key) {
+// (*ns: the namespace index of the flowId, CSlot.pad)
+__device__ uint32_t tab_find(const CSlot* __restrict__ tab, uint32_t mask, int64_t key, uint32_t* ns) {
     uint64_t h = tab_hash(key) & mask;
     for (uint32_t probe = 0; probe <= mask; ++probe) {
         const CSlot s = tab[h];
         if (s.idx == NO_FLOW) return NO_FLOW;
-        if (s.key == key) return s.idx;
+        if (s.key == key) { *ns = s.pad; return s.idx; }
         h = (h + 1) & mask;
     }
     return NO_FLOW;
 }
 
 // 1. DefaultTokenService.requestToken: notValidRequest -> BAD_REQUEST; no rule -> NO_RULE_EXISTS
+// nskeys / nsvals (optional, the namespace-grouped limiter): the request's namespace index, nns for a request that
+// tries no limiter, and its index -- the pairs the grouping sort starts from
 __global__ void k_tok_classify(const sg_token_req* __restrict__ req, uint64_t n, const CSlot* __restrict__ tab,
                                uint32_t mask, uint32_t* __restrict__ fidx, sg_token_result* __restrict__ res,
-                               uint32_t* __restrict__ flags) {
+                               uint32_t* __restrict__ flags, uint32_t* __restrict__ nskeys,
+                               uint32_t* __restrict__ nsvals, uint32_t nns) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const sg_token_req q = req[i];
     if (i > 0 && q.ts < req[i - 1].ts) atomicOr(flags, 1u);  // requests must be time-ordered
     sg_token_result r;
     r.status = SG_TOKEN_OK; r.remaining = 0; r.wait_in_ms = 0; r.reserved = 0;
-    uint32_t f = NO_FLOW;
+    uint32_t f = NO_FLOW, ns = 0;
     if (q.flow_id <= 0 || q.acquire_count <= 0) r.status = SG_TOKEN_BAD_REQUEST;
     else {
-        f = tab_find(tab, mask, q.flow_id);
+        f = tab_find(tab, mask, q.flow_id, &ns);
         if (f == NO_FLOW) r.status = SG_TOKEN_NO_RULE_EXISTS;
     }
     fidx[i] = f;
     res[i] = r;
+    if (nskeys) {
+        nskeys[i] = f == NO_FLOW || ns >= nns ? nns : ns;
+        nsvals[i] = (uint32_t)i;
+    }
 }
 
 // 2. GlobalRequestLimiter.tryPass of the namespace: RequestLimiter.canPass is
@@ -250,6 +259,117 @@ __global__ void k_lim_apply(const uint64_t n, const uint32_t* __restrict__ fidx,
     }
     keys[i] = key;
     vals[i] = (uint32_t)i;
+}
+
+// ---- 2'. the limiters of several namespaces (GlobalRequestLimiter.tryPass(namespace)): the candidates grouped by
+// namespace index (a stable radix sort of k_tok_classify's pairs: sk / sv, inside a namespace in request order, the
+// requests that try no limiter last under the key nns), so every namespace's 100 ms buckets are one run of sorted
+// positions and the namespaces are independent chains.
+// per sorted position: its (namespace, bucket) starts here.  small[1] = the number of candidates
+__global__ void k_nsl_flags(const sg_token_req* __restrict__ req, uint64_t n, const uint32_t* __restrict__ sk,
+                            const uint32_t* __restrict__ sv, uint32_t nns, uint32_t* __restrict__ bflag,
+                            uint32_t* __restrict__ small) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t ns = sk[p];
+    const uint32_t pns = p ? sk[p - 1] : 0xFFFFFFFFu;
+    uint32_t fl = 0;
+    if (ns < nns) {
+        fl = pns != ns || req[sv[p - 1]].ts / NS_WLEN != req[sv[p]].ts / NS_WLEN ? 1u : 0u;
+        if (p == n - 1) small[1] = (uint32_t)n;
+    } else if (p == 0 || pns < nns) small[1] = (uint32_t)p;
+    bflag[p] = fl;
+}
+// bstart[k] = first sorted position of the k-th (namespace, bucket); nsb[2 ns], nsb[2 ns + 1] = the namespace's
+// first bucket and one past its last (both 0, as cleared before, for a namespace with no candidate in the call)
+__global__ void k_nsl_starts(const uint32_t* __restrict__ sk, uint64_t n, uint32_t nns,
+                             const uint32_t* __restrict__ bflag, const uint32_t* __restrict__ bidx,
+                             uint32_t* __restrict__ bstart, uint32_t* __restrict__ nsb) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t ns = sk[p];
+    if (ns >= nns) return;
+    const uint32_t k = bidx[p];  // (exclusive: with bflag[p] the index of p's own bucket)
+    if (bflag[p]) {
+        bstart[k] = (uint32_t)p;
+        if (p == 0 || sk[p - 1] != ns) nsb[2 * ns] = k;
+    }
+    if (p == n - 1 || sk[p + 1] != ns) nsb[2 * ns + 1] = k + bflag[p];
+}
+// a wave per namespace walks its own buckets in order, against its own ring (lanes 0..9, as k_tok_limiter keeps
+// it) and limit: 64 buckets' (time, candidate count) loaded at once, then one uniform step per bucket
+// (RequestLimiter.canPass = sum(valid buckets) + 1 <= qpsAllowed, then add(1): the passes of a bucket are its
+// first kpass[k] candidates).  small[0] = buckets of the call, small[1] = candidates
+__global__ __launch_bounds__(64) void k_nsl_walk(const sg_token_req* __restrict__ req, const uint32_t* __restrict__ sv,
+                                                 const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ nsb,
+                                                 const uint32_t* __restrict__ small, NsLimiter* __restrict__ lims,
+                                                 const double* __restrict__ limits, uint32_t nns,
+                                                 uint32_t* __restrict__ kpass) {
+    const uint32_t ns = blockIdx.x, lane = threadIdx.x;
+    if (ns >= nns) return;
+    const uint32_t b0 = nsb[2 * ns], b1 = nsb[2 * ns + 1];
+    if (b0 >= b1) return;  // idle in this call: the ring stays as it is
+    const uint32_t nb = small[0], ncand = small[1];
+    const double lim = limits[ns];
+    const double allowed = lim < 0 ? 1.0 / 0.0 : lim;  // (negative: no limiter registered, tryPass -> true)
+    NsLimiter* L = lims + ns;
+    int64_t lws = lane < NS_BUCKETS ? L->ws[lane] : -1;
+    int64_t lcnt = lane < NS_BUCKETS ? L->cnt[lane] : 0;
+    for (uint32_t base = b0; base < b1; base += 64) {
+        const uint32_t k = base + lane;
+        int64_t t = 0;
+        uint32_t m = 0;
+        if (k < b1) {
+            const uint32_t a = bstart[k];
+            m = (k + 1 < nb ? bstart[k + 1] : ncand) - a;
+            t = req[sv[a]].ts;  // (every candidate of the bucket: the same bucket, the same valid set)
+        }
+        const uint32_t cnt = min(64u, b1 - base);
+        uint32_t mykp = 0;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const int64_t tb = __shfl(t, (int)j, 64);
+            const int64_t mj = (int64_t)__shfl(m, (int)j, 64);
+            const int64_t wsb = tb - tb % NS_WLEN;
+            const uint32_t idx = (uint32_t)((tb / NS_WLEN) % NS_BUCKETS);
+            if (lane == idx && (lws < 0 || wsb > lws)) { lws = wsb; lcnt = 0; }
+            int64_t s = (lane < NS_BUCKETS && lws >= 0 && tb - lws <= NS_INTERVAL) ? lcnt : 0;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
+            s = __shfl(s, 0, 64);
+            int64_t kp = 0;
+            if ((double)s + 1.0 <= allowed) {  // the j-th candidate passes iff (double)(s + j) + 1 <= allowed
+                int64_t lo = 0, hi = mj;
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi + 1) / 2;
+                    if ((double)(s + mid - 1) + 1.0 <= allowed) lo = mid; else hi = mid - 1;
+                }
+                kp = lo;
+            }
+            if (lane == idx) lcnt += kp;
+            if (lane == j) mykp = (uint32_t)kp;
+        }
+        if (k < b1) kpass[k] = mykp;
+    }
+    if (lane < NS_BUCKETS) { L->ws[lane] = lws; L->cnt[lane] = lcnt; }
+}
+// every sorted position: a candidate passes iff its rank in its bucket < kpass (else TOO_MANY_REQUEST); the flow
+// sort's pair, written at the request's own index (that sort then is stable in time order)
+__global__ void k_nsl_apply(const uint64_t n, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
+                            uint32_t nns, const uint32_t* __restrict__ fidx, const uint32_t* __restrict__ bflag,
+                            const uint32_t* __restrict__ bidx, const uint32_t* __restrict__ bstart,
+                            const uint32_t* __restrict__ kpass, uint32_t nflows, uint32_t* __restrict__ keys,
+                            uint32_t* __restrict__ vals, sg_token_result* __restrict__ res) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t i = sv[p];
+    uint32_t key = nflows;
+    if (sk[p] < nns) {
+        const uint32_t k = bidx[p] + bflag[p] - 1;
+        if ((uint32_t)p - bstart[k] < kpass[k]) key = fidx[i];
+        else res[i].status = SG_TOKEN_TOO_MANY_REQUEST;
+    }
+    keys[i] = key;
+    vals[i] = i;
 }
 
 // ---- 3. one flowId's requests, a workgroup of TF_T lanes, chunks of TF_T requests in time order.  A flow's cost is
@@ -527,10 +647,33 @@ __global__ __launch_bounds__(TF_T) void k_tok_flow_wg(const uint32_t* __restrict
 }
 
 hipError_t launch_tok_classify(const sg_token_req* req, uint64_t n, const CSlot* tab, uint32_t mask, uint32_t* fidx,
-                               sg_token_result* res, uint32_t* flags, hipStream_t st) {
+                               sg_token_result* res, uint32_t* flags, uint32_t* nskeys, uint32_t* nsvals, uint32_t nns,
+                               hipStream_t st) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_tok_classify, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, req, n, tab, mask, fidx, res,
-                       flags);
+                       flags, nskeys, nsvals, nns);
+    return hipGetLastError();
+}
+// the namespace-grouped limiter over the sorted pairs sk / sv (keys 0 .. nns).  bflag / bidx / bstart / kpass are
+// n-word scratch arrays, part the scan partials, small = 2 device words (buckets, candidates), nsb = 2 nns words;
+// keys / vals (not sk / sv) receive the flow sort's pairs
+hipError_t launch_tok_limiter_ns(const sg_token_req* req, uint64_t n, const uint32_t* sk, const uint32_t* sv,
+                                 const uint32_t* fidx, uint32_t nflows, NsLimiter* lims, const double* limits,
+                                 uint32_t nns, uint32_t* keys, uint32_t* vals, sg_token_result* res, uint32_t* bflag,
+                                 uint32_t* bidx, uint32_t* bstart, uint32_t* kpass, uint32_t* part, uint32_t* small,
+                                 uint32_t* nsb,
+                                 hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
+                                 hipStream_t st) {
+    if (!n) return hipSuccess;
+    const uint32_t g = (uint32_t)((n + 255) / 256);
+    hipError_t e = hipMemsetAsync(nsb, 0, (size_t)nns * 8, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_nsl_flags, dim3(g), dim3(256), 0, st, req, n, sk, sv, nns, bflag, small);
+    if ((e = scan(bflag, bidx, n, part, small, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_nsl_starts, dim3(g), dim3(256), 0, st, sk, n, nns, bflag, bidx, bstart, nsb);
+    hipLaunchKernelGGL(k_nsl_walk, dim3(nns), dim3(64), 0, st, req, sv, bstart, nsb, small, lims, limits, nns, kpass);
+    hipLaunchKernelGGL(k_nsl_apply, dim3(g), dim3(256), 0, st, n, sk, sv, nns, fidx, bflag, bidx, bstart, kpass, nflows,
+                       keys, vals, res);
     return hipGetLastError();
 }
 hipError_t launch_tok_limiter(const sg_token_req* req, uint64_t n, const uint32_t* fidx, uint32_t nflows,

@@ -159,7 +159,15 @@ hipError_t launch_decide_bin(int bin, const SEv* recs, const sg_event* ev, const
                              uint32_t* dec, uint32_t* bflags, hipStream_t st);
 // cluster.hip
 hipError_t launch_tok_classify(const sg_token_req* req, uint64_t n, const CSlot* tab, uint32_t mask, uint32_t* fidx,
-                               sg_token_result* res, uint32_t* flags, hipStream_t st);
+                               sg_token_result* res, uint32_t* flags, uint32_t* nskeys, uint32_t* nsvals, uint32_t nns,
+                               hipStream_t st);
+hipError_t launch_tok_limiter_ns(const sg_token_req* req, uint64_t n, const uint32_t* sk, const uint32_t* sv,
+                                 const uint32_t* fidx, uint32_t nflows, NsLimiter* lims, const double* limits,
+                                 uint32_t nns, uint32_t* keys, uint32_t* vals, sg_token_result* res, uint32_t* bflag,
+                                 uint32_t* bidx, uint32_t* bstart, uint32_t* kpass, uint32_t* part, uint32_t* small,
+                                 uint32_t* nsb,
+                                 hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
+                                 hipStream_t st);
 hipError_t launch_tok_limiter_par(const sg_token_req* req, uint64_t n, const uint32_t* fidx, uint32_t nflows,
                                   NsLimiter* lim, double allowed, uint32_t* keys, uint32_t* vals, sg_token_result* res,
                                   uint32_t* bflag, uint32_t* cflag, uint32_t* bidx, uint32_t* cexcl, uint32_t* bstart,
@@ -698,7 +706,16 @@ struct sg_engine {
     CSlot* d_ctab = nullptr;
     uint32_t ctab_mask = 0;
     uint64_t ncbkt = 0;
-    NsLimiter* d_nslim = nullptr;
+    NsLimiter* d_nslim = nullptr;                 // one RequestLimiter a namespace (SG_MAX_NAMESPACES of them)
+    // namespaces (GlobalRequestLimiter / ConnectionManager roles): index 0 = "default", always there
+    std::vector<std::string> ns_names;
+    std::unordered_map<std::string, uint32_t> ns_of;
+    std::vector<double> ns_limit;                 // qpsAllowed (negative: no limiter)
+    std::vector<int32_t> ns_conn;                 // connected count a flow of the namespace starts with
+    std::unordered_map<int64_t, uint32_t> flow_ns;  // flowId -> namespace index (absent: "default")
+    double* d_nslimit = nullptr;                  // ns_limit on the device (the grouped limiter reads it)
+    uint32_t* d_nsb = nullptr;                    // per namespace: its bucket range of the call (2 words)
+    bool tok_ns = false;                          // SG_TOK_NS=1: the grouped limiter with one namespace too
     sg_token_req* d_treq = nullptr;
     sg_token_result* d_tres = nullptr;
     uint32_t* d_tfidx = nullptr;
@@ -1326,6 +1343,12 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (const char* v = std::getenv("SG_RADIX_BELOW")) e->radix_below = std::strtoull(v, nullptr, 0);
     if (const char* v = std::getenv("SG_TOK_WIDE")) e->tok_wide = std::atoi(v) == 512 ? 512u : 1024u;
     if (const char* v = std::getenv("SG_TOK_LIGHT")) e->tok_light = (uint32_t)std::strtoul(v, nullptr, 0);
+    if (const char* v = std::getenv("SG_TOK_NS")) e->tok_ns = v[0] == '1';
+    // ServerConstants.DEFAULT_NAMESPACE: the limiter every flowId tries until it is assigned elsewhere
+    e->ns_names.push_back("default");
+    e->ns_of["default"] = 0;
+    e->ns_limit.push_back((double)cfg.cluster_max_allowed_qps);
+    e->ns_conn.push_back(0);
     if (const char* v = std::getenv("SG_J1_STREAM")) e->j1_stream = std::atoi(v);
     if (const char* v = std::getenv("SG_PQ")) e->pq_on = v[0] != '0';
     if (const char* v = std::getenv("SG_MIX")) e->mix_on = v[0] != '0';
@@ -1464,7 +1487,7 @@ int sg_engine_destroy(sg_engine* e) {
     for (auto& B : e->slot) free_slot(B);
     dfree(e->d_prio); dfree(e->d_hot_tab); dfree(e->d_hot_list); dfree(e->d_hot_part); dfree(e->d_hot_hb); dfree(e->d_comp); dfree(e->d_auxtab); dfree(e->d_auxpool); dfree(e->d_auxcnt); dfree(e->d_auxmeta);
     dfree(e->d_pflow); dfree(e->d_phot); dfree(e->d_pftab); dfree(e->d_pvtab); dfree(e->d_preq); dfree(e->d_pvals);
-    dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_borrow); dfree(e->d_keyring);
+    dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_nslimit); dfree(e->d_nsb); dfree(e->d_borrow); dfree(e->d_keyring);
     dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx); dfree(e->d_tbounds);
     dfree(e->d_snap_cnt); dfree(e->d_snap_off); dfree(e->d_snap_out); dfree(e->d_dbg);
     for (auto& B : e->slot)
@@ -1531,6 +1554,10 @@ static uint64_t tab_hash_h(int64_t k) {  // same mix as cluster.hip tab_hash
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+static uint32_t ns_index(const sg_engine* e, int64_t fid) {  // the flowId's namespace ("default" unless assigned)
+    auto it = e->flow_ns.find(fid);
+    return it == e->flow_ns.end() ? 0u : it->second;
+}
 static int rebuild_cluster(sg_engine* e, const sg_flow_rule* rules, uint32_t n) {
     std::vector<int64_t> order;                       // flowIds in first-appearance order
     std::unordered_map<int64_t, const sg_flow_rule*> rule_of;
@@ -1563,6 +1590,7 @@ static int rebuild_cluster(sg_engine* e, const sg_flow_rule* rules, uint32_t n) 
             f.flow_id = fid;
             f.n = r.cluster_sample_count;
             f.interval = r.cluster_window_interval_ms;
+            f.connected = e->ns_conn[ns_index(e, fid)];  // ConnectionManager.getConnectedCount(namespace)
             f.boff = (uint32_t)nb.size();
             CBkt z;
             std::memset(&z, 0, sizeof(z));
@@ -1583,6 +1611,7 @@ static int rebuild_cluster(sg_engine* e, const sg_flow_rule* rules, uint32_t n) 
         while (tab[h].idx != 0xFFFFFFFFu) h = (h + 1) & (cap - 1);
         tab[h].key = nf[i].flow_id;
         tab[h].idx = i;
+        tab[h].pad = ns_index(e, nf[i].flow_id);
     }
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab);
     e->d_cflow = nullptr; e->d_cbkt = nullptr; e->d_ctab = nullptr;
@@ -1764,6 +1793,7 @@ static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const
             f.flow_id = fid;
             f.n = r.cluster_sample_count;
             f.interval = r.cluster_window_interval_ms;
+            f.connected = e->ns_conn[ns_index(e, fid)];
             for (int k = 0; k < CP_MAXN; ++k) f.fws[k] = -1;
         }
         f.count = r.count;
@@ -1798,6 +1828,7 @@ static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const
         while (tab[h].idx != 0xFFFFFFFFu) h = (h + 1) & (cap - 1);
         tab[h].key = nf[i].flow_id;
         tab[h].idx = i;
+        tab[h].pad = ns_index(e, nf[i].flow_id);
     }
     dfree(e->d_pflow); dfree(e->d_phot); dfree(e->d_pftab);
     e->d_pflow = nullptr; e->d_phot = nullptr; e->d_pftab = nullptr;
@@ -3024,6 +3055,161 @@ int sg_cluster_set_connected_count(sg_engine* e, int64_t flow_id, int32_t connec
     return SG_OK;
 }
 
+// ---- namespaces: a RequestLimiter and a connected count each (GlobalRequestLimiter, ConnectionManager)
+// the limiters (never created), their limits and the grouped limiter's per-namespace words, on first use
+static int ensure_ns(sg_engine* e) {
+    if (e->d_nslim) return SG_OK;
+    std::vector<NsLimiter> z(SG_MAX_NAMESPACES);
+    for (auto& l : z)
+        for (int k = 0; k < NS_BUCKETS; ++k) { l.ws[k] = -1; l.cnt[k] = 0; }
+    std::vector<double> lim(SG_MAX_NAMESPACES, -1.0);
+    std::copy(e->ns_limit.begin(), e->ns_limit.end(), lim.begin());
+    if (!e->d_nslimit) HIPCHK(hipMalloc(&e->d_nslimit, SG_MAX_NAMESPACES * sizeof(double)));
+    if (!e->d_nsb) HIPCHK(hipMalloc(&e->d_nsb, SG_MAX_NAMESPACES * 2 * 4));
+    HIPCHK(hipMemcpy(e->d_nslimit, lim.data(), lim.size() * sizeof(double), hipMemcpyHostToDevice));
+    NsLimiter* d = nullptr;
+    HIPCHK(hipMalloc(&d, z.size() * sizeof(NsLimiter)));
+    if (hipMemcpy(d, z.data(), z.size() * sizeof(NsLimiter), hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(d);
+        return fail(SG_EDEVICE, "limiter initialisation failed");
+    }
+    e->d_nslim = d;
+    return SG_OK;
+}
+// The namespace-grouped limiter step: k_tok_classify left (namespace index, request) pairs in kin / vin; a stable
+// sort by namespace, then every namespace's limiter over its own run (cluster.hip 2').  On return kin / vin hold
+// the flow sort's pairs.  Scratch as launch_tok_limiter_par: the drained batch slot's arrays.
+static int tok_limiter_grouped(sg_engine* e, uint64_t n, uint32_t nflows, uint32_t*& kin, uint32_t*& vin,
+                               uint32_t*& kout, uint32_t*& vout) {
+    hipStream_t st = e->stream;
+    const uint32_t nns = (uint32_t)e->ns_names.size();
+    int bits = 1;
+    while (bits < 32 && (1ull << bits) <= nns) ++bits;  // keys 0..nns (nns = tries no limiter)
+    const int passes = (bits + 7) / 8;
+    const uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
+    for (int p = 0; p < passes; ++p) {
+        HIPCHK(launch_radix_hist(kin, n, p * 8, e->d_hist, nblocks, st));
+        HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks * 256, e->d_part, nullptr, st));
+        HIPCHK(launch_radix_scatter(kin, vin, n, p * 8, e->d_hist, nblocks, kout, vout, nullptr, st));
+        std::swap(kin, kout);
+        std::swap(vin, vout);
+    }
+    HIPCHK(launch_tok_limiter_ns(e->d_treq, n, kin, vin, e->d_tfidx, nflows, e->d_nslim, e->d_nslimit, nns, kout, vout,
+                                 e->d_tres, e->d_flag, e->d_pos, e->d_order, e->d_prev, e->d_part, e->d_small + 8,
+                                 e->d_nsb, launch_scan, st));
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+    return SG_OK;
+}
+// CSlot.pad of a loaded flowId table := the flowIds' namespace indices
+static int upload_ns_pads(sg_engine* e, CSlot* d_tab, uint32_t mask) {
+    if (!d_tab) return SG_OK;
+    std::vector<CSlot> tab((size_t)mask + 1);
+    HIPCHK(hipMemcpy(tab.data(), d_tab, tab.size() * sizeof(CSlot), hipMemcpyDeviceToHost));
+    for (auto& t : tab)
+        if (t.idx != 0xFFFFFFFFu) t.pad = ns_index(e, t.key);
+    HIPCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(CSlot), hipMemcpyHostToDevice));
+    return SG_OK;
+}
+
+int sg_cluster_namespace(sg_engine* e, const char* ns, double max_allowed_qps, uint32_t* out_ns_id) {
+    if (!e) return fail(SG_EINVAL, "null engine");
+    if (!ns || !ns[0]) return fail(SG_EINVAL, "namespace cannot be empty");  // AssertUtil.notEmpty
+    if (max_allowed_qps != max_allowed_qps) return fail(SG_EINVAL, "max_allowed_qps is not a number");
+    if (int rc = drain(e)) return rc;
+    auto it = e->ns_of.find(ns);
+    uint32_t id;
+    if (it != e->ns_of.end()) id = it->second;
+    else {
+        if (e->ns_names.size() >= SG_MAX_NAMESPACES) return fail(SG_ECAPACITY, "too many namespaces");
+        id = (uint32_t)e->ns_names.size();
+        e->ns_names.push_back(ns);
+        e->ns_of[ns] = id;
+        e->ns_limit.push_back(-1.0);
+        e->ns_conn.push_back(0);
+    }
+    // RequestLimiter.setQpsAllowed: the limit alone, the window stays
+    e->ns_limit[id] = max_allowed_qps;
+    if (e->d_nslimit)
+        HIPCHK(hipMemcpy(e->d_nslimit + id, &max_allowed_qps, sizeof(double), hipMemcpyHostToDevice));
+    if (out_ns_id) *out_ns_id = id;
+    return SG_OK;
+}
+
+int sg_cluster_assign_flows(sg_engine* e, const char* ns, const int64_t* flow_ids, uint32_t n) {
+    if (!e || !ns || (n && !flow_ids)) return fail(SG_EINVAL, "null argument");
+    auto it = e->ns_of.find(ns);
+    if (it == e->ns_of.end()) return fail(SG_ENOTFOUND, "namespace is not registered");
+    const uint32_t id = it->second;
+    bool changes = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (flow_ids[i] <= 0) return fail(SG_EINVAL, "flowId must be positive");
+        auto f = e->flow_ns.find(flow_ids[i]);
+        if (f == e->flow_ns.end()) changes = true;
+        else if (f->second != id) return fail(SG_ESTATE, "flowId belongs to another namespace");
+    }
+    if (!changes) return SG_OK;
+    if (int rc = drain(e)) return rc;
+    for (uint32_t i = 0; i < n; ++i) e->flow_ns[flow_ids[i]] = id;
+    if (int rc = upload_ns_pads(e, e->d_ctab, e->ctab_mask)) return rc;
+    return upload_ns_pads(e, e->d_pftab, e->pftab_mask);
+}
+
+int sg_cluster_set_namespace_connected(sg_engine* e, const char* ns, int32_t connected) {
+    if (!e || !ns) return fail(SG_EINVAL, "null argument");
+    auto it = e->ns_of.find(ns);
+    if (it == e->ns_of.end()) return fail(SG_ENOTFOUND, "namespace is not registered");
+    const uint32_t id = it->second;
+    if (int rc = drain(e)) return rc;
+    e->ns_conn[id] = connected;
+    // every loaded flow of the namespace (the metric state lives on the device: read, patch, write back)
+    bool any = false;
+    for (auto& f : e->cflows) any = any || ns_index(e, f.flow_id) == id;
+    if (any) {
+        std::vector<CFlow> cur(e->cflows.size());
+        HIPCHK(hipMemcpy(cur.data(), e->d_cflow, cur.size() * sizeof(CFlow), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cur.size(); ++i)
+            if (ns_index(e, cur[i].flow_id) == id) { cur[i].connected = connected; e->cflows[i].connected = connected; }
+        HIPCHK(hipMemcpy(e->d_cflow, cur.data(), cur.size() * sizeof(CFlow), hipMemcpyHostToDevice));
+    }
+    any = false;
+    for (auto& f : e->pflows) any = any || ns_index(e, f.flow_id) == id;
+    if (any) {
+        std::vector<PFlow> cur(e->pflows.size());
+        HIPCHK(hipMemcpy(cur.data(), e->d_pflow, cur.size() * sizeof(PFlow), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cur.size(); ++i)
+            if (ns_index(e, cur[i].flow_id) == id) { cur[i].connected = connected; e->pflows[i].connected = connected; }
+        HIPCHK(hipMemcpy(e->d_pflow, cur.data(), cur.size() * sizeof(PFlow), hipMemcpyHostToDevice));
+    }
+    return SG_OK;
+}
+
+int sg_cluster_namespace_qps(sg_engine* e, const char* ns, int64_t now_ms, double* current_qps,
+                             double* max_allowed_qps) {
+    if (!e || !ns) return fail(SG_EINVAL, "null argument");
+    auto it = e->ns_of.find(ns);
+    if (it == e->ns_of.end()) return fail(SG_ENOTFOUND, "namespace is not registered");
+    if (now_ms < 0) return fail(SG_EINVAL, "negative time");
+    const uint32_t id = it->second;
+    if (int rc = drain(e)) return rc;
+    int64_t sum = 0;
+    if (e->d_nslim) {
+        NsLimiter l;
+        HIPCHK(hipMemcpy(&l, e->d_nslim + id, sizeof(l), hipMemcpyDeviceToHost));
+        // LeapArray.values(now) after currentWindow(now): the slot of now counts only with now's own window
+        const int cur = (int)((now_ms / NS_WLEN) % NS_BUCKETS);
+        const int64_t wsn = now_ms - now_ms % NS_WLEN;
+        for (int k = 0; k < NS_BUCKETS; ++k) {
+            if (l.ws[k] < 0 || now_ms - l.ws[k] > NS_INTERVAL) continue;
+            if (k == cur && l.ws[k] < wsn) continue;
+            sum += l.cnt[k];
+        }
+    }
+    if (current_qps) *current_qps = (double)sum / (NS_INTERVAL / 1000.0);
+    if (max_allowed_qps) *max_allowed_qps = e->ns_limit[id];
+    return SG_OK;
+}
+
 // Batched DefaultTokenService.requestToken (see cluster.hip for the device steps).
 int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n, sg_token_result* out) {
     if (!e || (n && (!reqs || !out))) return fail(SG_EINVAL, "null argument");
@@ -3041,12 +3227,7 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
         HIPCHK(hipMalloc(&e->d_tfidx, c * 4));
         e->tcap = c;
     }
-    if (!e->d_nslim) {
-        HIPCHK(hipMalloc(&e->d_nslim, sizeof(NsLimiter)));
-        NsLimiter z;
-        for (int k = 0; k < NS_BUCKETS; ++k) { z.ws[k] = -1; z.cnt[k] = 0; }
-        HIPCHK(hipMemcpy(e->d_nslim, &z, sizeof(z), hipMemcpyHostToDevice));
-    }
+    if (int rc2 = ensure_ns(e)) return rc2;
     if (!e->d_ctab) {  // no cluster rule loaded yet: an empty table
         CSlot t[16];
         for (auto& x : t) { x.key = 0; x.idx = 0xFFFFFFFFu; x.pad = 0; }
@@ -3058,23 +3239,29 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
     // requests and results may be host or device memory (dist.request_tokens keeps them in HBM under RCCL)
     HIPCHK(hipMemcpyAsync(e->d_treq, reqs, n * sizeof(sg_token_req), hipMemcpyDefault, st));
     HIPCHK(hipMemsetAsync(e->d_small, 0, 4, st));
-    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_ctab, e->ctab_mask, e->d_tfidx, e->d_tres, e->d_small, st));
+    const uint32_t nns = (uint32_t)e->ns_names.size();
+    const bool grouped = nns > 1 || e->tok_ns;  // several limiters: the namespace-grouped limiter step
+    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_ctab, e->ctab_mask, e->d_tfidx, e->d_tres, e->d_small,
+                               grouped ? e->d_k0 : nullptr, grouped ? e->d_v0 : nullptr, nns, st));
     uint32_t flags = 0;
     HIPCHK(hipMemcpyAsync(&flags, e->d_small, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (flags & 1) return fail(SG_EINVAL, "token requests must be ordered by ts (the replay clock)");
     // GlobalRequestLimiter: a negative qpsAllowed stands for "no limiter registered" (tryPass -> true)
-    const double allowed = e->cfg.cluster_max_allowed_qps < 0 ? 1.0 / 0.0 : (double)e->cfg.cluster_max_allowed_qps;
+    const double allowed = e->ns_limit[0] < 0 ? 1.0 / 0.0 : e->ns_limit[0];
     // the limiter (parallel per 100 ms bucket; the drained batch slot's arrays are its scratch), then the flows
-    HIPCHK(launch_tok_limiter_par(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0, e->d_tres,
-                                  e->d_flag, e->d_pos, e->d_order, e->d_prev, e->d_dec, e->d_posof, e->d_part,
-                                  e->d_small + 8, launch_scan, st));
+    uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
+    if (grouped) {
+        if (int rc2 = tok_limiter_grouped(e, n, nflows, kin, vin, kout, vout)) return rc2;
+    } else
+        HIPCHK(launch_tok_limiter_par(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0,
+                                      e->d_tres, e->d_flag, e->d_pos, e->d_order, e->d_prev, e->d_dec, e->d_posof,
+                                      e->d_part, e->d_small + 8, launch_scan, st));
     if (nflows) {
         int bits = 1;
         while (bits < 32 && (1ull << bits) <= nflows) ++bits;  // keys 0..nflows (nflows = not for a flow)
         const int passes = (bits + 7) / 8;
         const uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
-        uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
         for (int p = 0; p < passes; ++p) {
             HIPCHK(launch_radix_hist(kin, n, p * 8, e->d_hist, nblocks, st));
             HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks * 256, e->d_part, nullptr, st));
@@ -3129,12 +3316,7 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
         e->pvcap = std::max<uint64_t>(n_values, 1u << 16);
         HIPCHK(hipMalloc(&e->d_pvals, e->pvcap * sizeof(uint64_t)));
     }
-    if (!e->d_nslim) {
-        HIPCHK(hipMalloc(&e->d_nslim, sizeof(NsLimiter)));
-        NsLimiter z;
-        for (int k = 0; k < NS_BUCKETS; ++k) { z.ws[k] = -1; z.cnt[k] = 0; }
-        HIPCHK(hipMemcpy(e->d_nslim, &z, sizeof(z), hipMemcpyHostToDevice));
-    }
+    if (int rc2 = ensure_ns(e)) return rc2;
     if (!e->d_pftab) {  // no cluster param rule loaded yet: an empty table
         CSlot t[16];
         for (auto& x : t) { x.key = 0; x.idx = 0xFFFFFFFFu; x.pad = 0; }
@@ -3154,19 +3336,26 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
     HIPCHK(hipMemcpyAsync(e->d_preq, reqs, n * sizeof(sg_param_token_req), hipMemcpyHostToDevice, st));
     if (n_values) HIPCHK(hipMemcpyAsync(e->d_pvals, values, n_values * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(e->d_small, 0, 4, st));
-    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_pftab, e->pftab_mask, e->d_tfidx, e->d_tres, e->d_small, st));
+    const uint32_t nns = (uint32_t)e->ns_names.size();
+    const bool grouped = nns > 1 || e->tok_ns;
+    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_pftab, e->pftab_mask, e->d_tfidx, e->d_tres, e->d_small,
+                               grouped ? e->d_k0 : nullptr, grouped ? e->d_v0 : nullptr, nns, st));
     uint32_t flags = 0;
     HIPCHK(hipMemcpyAsync(&flags, e->d_small, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (flags & 1) return fail(SG_EINVAL, "token requests must be ordered by ts (the replay clock)");
-    const double allowed = e->cfg.cluster_max_allowed_qps < 0 ? 1.0 / 0.0 : (double)e->cfg.cluster_max_allowed_qps;
-    HIPCHK(launch_tok_limiter(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0, e->d_tres, st));
+    const double allowed = e->ns_limit[0] < 0 ? 1.0 / 0.0 : e->ns_limit[0];
+    uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
+    if (grouped) {
+        if (int rc2 = tok_limiter_grouped(e, n, nflows, kin, vin, kout, vout)) return rc2;
+    } else
+        HIPCHK(launch_tok_limiter(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0, e->d_tres,
+                                  st));
     if (nflows) {
         int bits = 1;
         while (bits < 32 && (1ull << bits) <= nflows) ++bits;
         const int passes = (bits + 7) / 8;
         const uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
-        uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
         for (int p = 0; p < passes; ++p) {
             HIPCHK(launch_radix_hist(kin, n, p * 8, e->d_hist, nblocks, st));
             HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks * 256, e->d_part, nullptr, st));

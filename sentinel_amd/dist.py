@@ -13,9 +13,12 @@ resources, still no data-path traffic.  Two exchanges remain, and they live here
   node).  Resource ids are local to a rank's engine, so each row carries its rank in ``reserved``.
 * ``request_tokens``: token requests go to the token-server rank.  The namespace's
   GlobalRequestLimiter (csrv/flow/statistic/limit/GlobalRequestLimiter.java:46-54) is shared by all
-  flowIds of the namespace, so the exact server is one engine: every rank's requests are gathered
-  there, decided in one merged time order (ts, rank, local order), and the results broadcast back.
-  The server's request rate is bounded by that same limiter, so one GPU is plenty.
+  flowIds of the namespace, so the exact server is one engine per namespace: every rank's requests
+  are gathered there, decided in one merged time order (ts, rank, local order), and the results
+  broadcast back.  The engine keeps a limiter per namespace (``sg_cluster_namespace``), so namespaces
+  could go to different ranks; this module still sends all of them to one token-server rank (routing
+  by namespace is the follow-up).  A namespace's request rate is bounded by its own
+  limiter, so one GPU is plenty for it.
 """
 from __future__ import annotations
 

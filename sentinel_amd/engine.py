@@ -25,6 +25,8 @@ EXPORTS = (
     "sg_submit_async", "sg_sync", "sg_snapshot_metrics", "sg_cluster_set_connected_count",
     "sg_cluster_request_tokens", "sg_cluster_request_param_tokens", "sg_read_node", "sg_last_error", "sg_last_timings",
     "sg_submit_ex", "sg_submit_ex_async", "sg_intern_origin", "sg_intern_context", "sg_param_thread_count",
+    "sg_cluster_namespace", "sg_cluster_assign_flows", "sg_cluster_set_namespace_connected",
+    "sg_cluster_namespace_qps",
 )
 
 
@@ -61,6 +63,10 @@ def lib():
         L.sg_cluster_set_connected_count.argtypes = [P, C.c_int64, C.c_int32]
         L.sg_cluster_request_tokens.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p]
         L.sg_cluster_request_param_tokens.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.sg_cluster_namespace.argtypes = [P, C.c_char_p, C.c_double, C.POINTER(C.c_uint32)]
+        L.sg_cluster_assign_flows.argtypes = [P, C.c_char_p, C.POINTER(C.c_int64), C.c_uint32]
+        L.sg_cluster_set_namespace_connected.argtypes = [P, C.c_char_p, C.c_int32]
+        L.sg_cluster_namespace_qps.argtypes = [P, C.c_char_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sg_read_node.argtypes = [P, C.c_uint32, C.c_int64, C.POINTER(A.SgNodeState)]
         L.sg_last_error.restype = C.c_char_p
         L.sg_last_timings.argtypes = [P, C.POINTER(C.c_double), C.c_int]
@@ -297,6 +303,29 @@ class Engine:
     # ---- token server (sg_cluster_*; DefaultTokenService.requestToken, csrv/flow/DefaultTokenService.java:37-48)
     def cluster_set_connected(self, flow_id: int, n: int):
         _check(lib().sg_cluster_set_connected_count(self.h, int(flow_id), int(n)))
+
+    # ---- namespaces: a GlobalRequestLimiter and a connected count each (csrv/flow/statistic/limit/
+    # GlobalRequestLimiter.java:30-80, ConnectionManager.getConnectedCount(namespace))
+    def cluster_namespace(self, name, max_qps: float) -> int:
+        """Register a namespace, or change a registered one's limit (its window stays); returns its dense id."""
+        out = C.c_uint32()
+        _check(lib().sg_cluster_namespace(self.h, None if name is None else str(name).encode(), float(max_qps),
+                                          C.byref(out)))
+        return out.value
+
+    def cluster_assign_flows(self, name: str, flow_ids):
+        """The flowIds (cluster flow rules and cluster param rules alike) of a registered namespace."""
+        ids = np.ascontiguousarray(flow_ids, dtype=np.int64).reshape(-1)
+        _check(lib().sg_cluster_assign_flows(self.h, name.encode(), ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids)))
+
+    def cluster_set_namespace_connected(self, name: str, n: int):
+        _check(lib().sg_cluster_set_namespace_connected(self.h, name.encode(), int(n)))
+
+    def cluster_namespace_qps(self, name: str, now: int):
+        """(GlobalRequestLimiter.getCurrentQps at now, getMaxAllowedQps) of the namespace; a read-back."""
+        cur, lim = C.c_double(), C.c_double()
+        _check(lib().sg_cluster_namespace_qps(self.h, name.encode(), int(now), C.byref(cur), C.byref(lim)))
+        return cur.value, lim.value
 
     def cluster_request_array(self, reqs: np.ndarray) -> np.ndarray:
         """reqs: A.TOKEN_REQ_DTYPE array (time-ordered) -> A.TOKEN_RES_DTYPE array."""

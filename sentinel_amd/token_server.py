@@ -250,13 +250,27 @@ class TokenServer:
     `cluster_request_array(A.TOKEN_REQ_DTYPE array)` and `cluster_set_connected(flow_id, n)`.
     `flow_namespaces` maps flowId -> namespace (ClusterFlowRuleManager's namespace of a rule) so a
     ping updates the AVG_LOCAL connected count of every flow of its namespace.  `clock` returns ms
-    (TimeUtil.currentTimeMillis); tests inject a replay clock.  `max_batch` bounds one device call."""
+    (TimeUtil.currentTimeMillis); tests inject a replay clock.  `max_batch` bounds one device call.
+    `namespace_qps` maps namespace -> maxAllowedQps (ClusterServerConfigManager.getMaxAllowedQps(namespace)):
+    when given, every namespace gets a GlobalRequestLimiter of its own on the device
+    (`cluster_namespace`), the flowIds of `flow_namespaces` are assigned to them (`cluster_assign_flows`)
+    before the first request is served, and a ping or a disconnect makes one
+    `cluster_set_namespace_connected` call.  None: one limiter for all, and per-flow connected counts."""
 
     def __init__(self, service, flow_namespaces: Optional[Dict[int, str]] = None,
                  clock: Optional[Callable[[], int]] = None, max_batch: int = 65536, record: bool = False,
-                 param_key: Optional[Callable[[str, str], int]] = None):
+                 param_key: Optional[Callable[[str, str], int]] = None,
+                 namespace_qps: Optional[Dict[str, float]] = None):
         self.service = service
         self.flow_ns = dict(flow_namespaces or {})
+        self.ns_qps = None if namespace_qps is None else dict(namespace_qps)
+        if self.ns_qps is not None:
+            for ns, qps in self.ns_qps.items():
+                service.cluster_namespace(ns, qps)
+            for ns in self.ns_qps:
+                fids = [fid for fid, n in self.flow_ns.items() if n == ns]
+                if fids:
+                    service.cluster_assign_flows(ns, fids)
         self.clock = clock or (lambda: int(time.time() * 1000))
         self.max_batch = max_batch
         self.record = record
@@ -289,6 +303,9 @@ class TokenServer:
 
     def _update_connected(self, namespace: str):
         n = self.conns.count(namespace)
+        if self.ns_qps is not None and namespace in self.ns_qps:
+            self.service.cluster_set_namespace_connected(namespace, n)
+            return
         for fid, ns in self.flow_ns.items():
             if ns == namespace:
                 self.service.cluster_set_connected(fid, n)
