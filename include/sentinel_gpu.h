@@ -59,6 +59,7 @@ enum {
     SG_CLUSTER_THRESHOLD_AVG_LOCAL = 0,
     SG_CLUSTER_THRESHOLD_GLOBAL = 1
 };
+enum { SG_AUTHORITY_WHITE = 0, SG_AUTHORITY_BLACK = 1 };   /* RuleConstant.AUTHORITY_* */
 
 /* ---- engine configuration ---------------------------------------------- */
 typedef struct sg_config {
@@ -153,6 +154,14 @@ typedef struct sg_param_rule {
     int32_t cluster_window_interval_ms;
 } sg_param_rule;
 
+/* core/slots/block/authority/AuthorityRule.java */
+typedef struct sg_authority_rule {
+    const char* resource;
+    const char* limit_app;            /* comma-separated origin names, compared verbatim (no trimming) */
+    int32_t strategy;                 /* default WHITE; neither WHITE nor BLACK: valid, never blocks */
+    int32_t reserved;
+} sg_authority_rule;
+
 /* ---- events ----------------------------------------------------------------
  * One 24-byte record per SphU.entry / Entry.exit / Tracer.trace, in
  * non-decreasing ts order (ties keep submission order).  ts is the value
@@ -168,10 +177,12 @@ enum {
                                    with ext.n_args > 0 takes the args from the table instead) */
     SG_F_EXIT_ARGS = 1u << 2,   /* Entry.exit(count, args): param thread counts are released (EXIT), SURVEY Q14 */
     SG_F_ENTRY_OUT = 1u << 3,   /* EntryType.OUT (ENTRY); informational (SystemSlot is out of scope) */
-    SG_F_BLOCKED_UPSTREAM = 1u << 4 /* ENTRY: the caller's SystemSlot / AuthoritySlot threw.  Those slots sit between
-                                   ParamFlowSlot and FlowSlot (param/slots/HotParamSlotChainBuilder.java:39-50), so the
-                                   param checks still run (and may block first); otherwise the entry is blocked with
-                                   SG_BLOCK_UPSTREAM and StatisticSlot counts the block (StatisticSlot.java:97-117) */
+    SG_F_BLOCKED_UPSTREAM = 1u << 4 /* ENTRY: the caller's SystemSlot threw (or an AuthoritySlot the caller chose to keep
+                                   instead of sg_load_authority_rules).  Those slots sit between ParamFlowSlot and
+                                   FlowSlot (param/slots/HotParamSlotChainBuilder.java:39-50), so the param checks still
+                                   run (and may block first); otherwise the entry is blocked with SG_BLOCK_UPSTREAM --
+                                   before the engine's own authority check, as SystemSlot precedes AuthoritySlot -- and
+                                   StatisticSlot counts the block (StatisticSlot.java:97-117) */
 };
 /* EXIT/TRACE aux: low 48 bits = global index of the ENTRY event this refers
  * to (SG_REF_NONE = the caller asserts the entry passed); EXIT bits 48..63 =
@@ -229,7 +240,10 @@ enum {
     SG_BLOCK_DEGRADE = 3, /* DegradeException    core/slots/block/degrade/DegradeRuleManager.java:82 */
     SG_BLOCK_PARAM = 4,   /* ParamFlowException  param/slots/block/flow/param/ParamFlowSlot.java:98 */
     SG_NO_CHECK = 5,      /* no slot chain (MAX_SLOT_CHAIN_SIZE), NullContext, or Constants.ON == false */
-    SG_BLOCK_UPSTREAM = 6,/* SG_F_BLOCKED_UPSTREAM: SystemBlockException / AuthorityException of the caller's slots */
+    SG_BLOCK_UPSTREAM = 6,/* SG_F_BLOCKED_UPSTREAM: SystemBlockException of the caller's SystemSlot (or the
+                             AuthorityException of an AuthoritySlot the caller kept) */
+    SG_BLOCK_AUTHORITY = 7,/* AuthorityException: the resource's authority rule (sg_load_authority_rules) rejects the
+                             entry's origin (core/slots/block/authority/AuthoritySlot.java:48-65); rule slot 0, wait 0 */
     SG_NOT_ENTRY = 0xFF   /* EXIT / TRACE record */
 };
 #define SG_DECISION_STATUS(d) ((d) & 0xFFu)
@@ -328,6 +342,17 @@ int sg_resource_id(sg_engine* e, const char* name, uint32_t* out_id);
 int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint32_t* n_loaded);
 int sg_load_degrade_rules(sg_engine* e, const sg_degrade_rule* rules, uint32_t n, uint32_t* n_loaded);
 int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, uint32_t* n_loaded);
+
+/* AuthorityRuleManager.loadRules (core/slots/block/authority/AuthorityRuleManager.java:105-157): a rule is valid
+ * iff its resource and its limit_app are not blank and strategy >= 0; the first valid rule of a resource in list
+ * order is kept, later ones are ignored; *n_loaded (optional) receives the number kept.  n == 0 (rules may be NULL)
+ * clears the rules; an equal list is a no-op; the rules do not count against cfg.max_rules.  The check is
+ * AuthorityRuleChecker.passCheck (AuthorityRuleChecker.java:30-65) on the origin of the entry's sg_event_ext: the
+ * empty origin passes; otherwise BLACK blocks an origin that equals one of limit_app.split(","), WHITE one that
+ * equals none.  It runs where AuthoritySlot sits: after the entry's param rules and after SG_F_BLOCKED_UPSTREAM,
+ * before the first flow rule; a blocked entry is SG_BLOCK_AUTHORITY and is counted as any blocked entry.  Loading
+ * interns no origin: a listed name takes effect once sg_intern_origin has given it an id. */
+int sg_load_authority_rules(sg_engine* e, const sg_authority_rule* rules, uint32_t n, uint32_t* n_loaded);
 
 /* Interns a parameter value exactly as ParamFlowRuleUtil.parseItemValue would
  * type it (param/.../ParamFlowRuleUtil.java:85-121): the key of Integer 1 differs

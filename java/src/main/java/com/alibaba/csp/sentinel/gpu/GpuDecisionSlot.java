@@ -12,7 +12,7 @@ import com.alibaba.csp.sentinel.slotchain.ProcessorSlotEntryCallback;
 import com.alibaba.csp.sentinel.slotchain.ProcessorSlotExitCallback;
 import com.alibaba.csp.sentinel.slotchain.ResourceWrapper;
 import com.alibaba.csp.sentinel.slots.block.BlockException;
-import com.alibaba.csp.sentinel.slots.block.authority.AuthoritySlot;
+import com.alibaba.csp.sentinel.slots.block.authority.AuthorityException;
 import com.alibaba.csp.sentinel.slots.block.degrade.DegradeException;
 import com.alibaba.csp.sentinel.slots.block.degrade.DegradeRule;
 import com.alibaba.csp.sentinel.slots.block.flow.FlowException;
@@ -28,11 +28,12 @@ import com.alibaba.csp.sentinel.util.TimeUtil;
  * The GPU-decided part of HotParamSlotChainBuilder's chain (param/slots/HotParamSlotChainBuilder.java:38-51):
  * StatisticSlot -> ParamFlowSlot -> SystemSlot -> AuthoritySlot -> FlowSlot -> DegradeSlot in one slot.
  *
- * <p>SystemSlot and AuthoritySlot stay on the JVM (their inputs -- system load, the origin's black/white
- * list -- live here) and run first; a BlockException of theirs is passed to the engine as
- * SG_F_BLOCKED_UPSTREAM, so the param checks that precede them in the reference still run and may block
- * first.  The engine decides everything else and keeps the resource, origin and context statistics
- * (StatisticSlot.entry/exit, StatisticSlot.java:54-173) on the device; the JVM keeps
+ * <p>SystemSlot stays on the JVM (its inputs -- system load, the global ENTRY_NODE -- live here) and runs
+ * first; its BlockException is passed to the engine as SG_F_BLOCKED_UPSTREAM, so the param checks that
+ * precede it in the reference still run and may block first.  AuthoritySlot is the engine's: GpuRuleSync
+ * mirrors AuthorityRuleManager's rules to the device, and a decision of SG_BLOCK_AUTHORITY becomes the
+ * AuthorityException the reference throws.  The engine decides everything else and keeps the resource,
+ * origin and context statistics (StatisticSlot.entry/exit, StatisticSlot.java:54-173) on the device; the JVM keeps
  * {@link Constants#ENTRY_NODE} and the registered entry/exit callbacks, minus the hot-parameter ones
  * whose thread counts the engine keeps itself.
  */
@@ -41,7 +42,6 @@ public class GpuDecisionSlot extends AbstractLinkedProcessorSlot<DefaultNode> {
     private static final String PARAM_PKG = "com.alibaba.csp.sentinel.slots.block.flow.param.";
 
     private final SystemSlot system = new SystemSlot();
-    private final AuthoritySlot authority = new AuthoritySlot();
     /** Passed entries of every chain (one slot instance per resource) awaiting their exit. */
     private static final ConcurrentHashMap<Entry, GpuEngine.Op> LIVE = new ConcurrentHashMap<>();
 
@@ -68,7 +68,6 @@ public class GpuDecisionSlot extends AbstractLinkedProcessorSlot<DefaultNode> {
         BlockException upstream = null;
         try {
             system.entry(context, resourceWrapper, node, count, prioritized, args);    // no next slot: checks only
-            authority.entry(context, resourceWrapper, node, count, prioritized, args);
         } catch (BlockException be) {
             upstream = be;
         }
@@ -134,7 +133,7 @@ public class GpuDecisionSlot extends AbstractLinkedProcessorSlot<DefaultNode> {
             default:
                 break;
         }
-        BlockException e = blockOf(status, SentinelGpu.ruleSlot(d), name, args, upstream);
+        BlockException e = blockOf(status, SentinelGpu.ruleSlot(d), name, args, upstream, context.getOrigin());
         context.getCurEntry().setError(e);
         if (in) {
             Constants.ENTRY_NODE.increaseBlockQps(count);
@@ -147,7 +146,8 @@ public class GpuDecisionSlot extends AbstractLinkedProcessorSlot<DefaultNode> {
         throw e;
     }
 
-    private static BlockException blockOf(int status, int slot, String name, Object[] args, BlockException upstream) {
+    private static BlockException blockOf(int status, int slot, String name, Object[] args, BlockException upstream,
+                                          String origin) {
         switch (status) {
             case SentinelGpu.BLOCK_FLOW: {
                 FlowRule r = GpuRuleSync.flowRule(name, slot);
@@ -165,6 +165,8 @@ public class GpuDecisionSlot extends AbstractLinkedProcessorSlot<DefaultNode> {
                 }
                 return new ParamFlowException(name, triggered, r);
             }
+            case SentinelGpu.BLOCK_AUTHORITY:   // AuthoritySlot.checkBlackWhiteAuthority (AuthoritySlot.java:48-65)
+                return new AuthorityException(origin, GpuRuleSync.authorityRule(name));
             case SentinelGpu.BLOCK_UPSTREAM:
                 if (upstream != null) {
                     return upstream;

@@ -15,6 +15,8 @@ import java.util.Set;
 import com.alibaba.csp.sentinel.property.PropertyListener;
 import com.alibaba.csp.sentinel.property.SentinelProperty;
 import com.alibaba.csp.sentinel.slots.block.RuleConstant;
+import com.alibaba.csp.sentinel.slots.block.authority.AuthorityRule;
+import com.alibaba.csp.sentinel.slots.block.authority.AuthorityRuleManager;
 import com.alibaba.csp.sentinel.slots.block.degrade.DegradeRule;
 import com.alibaba.csp.sentinel.slots.block.degrade.DegradeRuleManager;
 import com.alibaba.csp.sentinel.slots.block.flow.FlowRule;
@@ -27,9 +29,9 @@ import com.alibaba.csp.sentinel.util.StringUtil;
 import static java.lang.foreign.ValueLayout.JAVA_INT;
 
 /**
- * Keeps the device rule tables equal to the three rule managers.  Each manager holds its rules in a
+ * Keeps the device rule tables equal to the four rule managers.  Each manager holds its rules in a
  * private {@code currentProperty} (FlowRuleManager.java:52, DegradeRuleManager.java:49,
- * ParamFlowRuleManager.java:45) that every loadRules / register2Property goes through; this class adds
+ * ParamFlowRuleManager.java:45, AuthorityRuleManager.java:45) that every loadRules / register2Property goes through; this class adds
  * one more {@link PropertyListener} to it, which pushes the new list through sg_load_*_rules (the engine
  * validates, de-duplicates and orders exactly as the managers do).  A register2Property swaps the
  * property object; {@link #rehook} (called by the batcher before every batch) follows the swap.
@@ -39,11 +41,13 @@ import static java.lang.foreign.ValueLayout.JAVA_INT;
  */
 final class GpuRuleSync {
 
-    private static final Field[] FIELDS = new Field[3];
-    private static final Object[] HOOKED = new Object[3];
+    private static final Field[] FIELDS = new Field[4];
+    private static final Object[] HOOKED = new Object[4];
 
     static volatile Map<String, List<FlowRule>> flowByResource = Collections.emptyMap();
     static volatile Map<String, List<DegradeRule>> degradeByResource = Collections.emptyMap();
+    /** The rule AuthorityRuleManager keeps per resource: the first valid one (loadAuthorityConf). */
+    static volatile Map<String, AuthorityRule> authorityByResource = Collections.emptyMap();
 
     private static GpuEngine engine;
 
@@ -55,6 +59,7 @@ final class GpuRuleSync {
             FIELDS[0] = FlowRuleManager.class.getDeclaredField("currentProperty");
             FIELDS[1] = DegradeRuleManager.class.getDeclaredField("currentProperty");
             FIELDS[2] = ParamFlowRuleManager.class.getDeclaredField("currentProperty");
+            FIELDS[3] = AuthorityRuleManager.class.getDeclaredField("currentProperty");
             for (Field f : FIELDS) {
                 f.setAccessible(true);
             }
@@ -67,7 +72,7 @@ final class GpuRuleSync {
     /** Hook any manager whose property object changed since the last call (cheap when none did). */
     @SuppressWarnings("unchecked")
     static void rehook() {
-        for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < 4; k++) {
             Object p;
             try {
                 p = FIELDS[k].get(null);
@@ -90,8 +95,12 @@ final class GpuRuleSync {
                         ((SentinelProperty<List<DegradeRule>>)p).addListener(
                             new Listener<>(GpuRuleSync::loadDegrade));
                         break;
-                    default:
+                    case 2:
                         ((SentinelProperty<List<ParamFlowRule>>)p).addListener(new Listener<>(GpuRuleSync::loadParam));
+                        break;
+                    default:
+                        ((SentinelProperty<List<AuthorityRule>>)p).addListener(
+                            new Listener<>(GpuRuleSync::loadAuthority));
                 }
             }
         }
@@ -167,6 +176,24 @@ final class GpuRuleSync {
             push(SentinelGpu.LOAD_PARAM_RULES, NativeRules.param(a, rules), rules.size(), "param");
         }
         // the rule objects of a block come from ParamFlowRuleManager.getRulesOfResource, same order
+    }
+
+    static void loadAuthority(List<AuthorityRule> rules) {
+        try (Arena a = Arena.ofConfined()) {
+            push(SentinelGpu.LOAD_AUTHORITY_RULES, NativeRules.authority(a, rules), rules.size(), "authority");
+        }
+        // AuthorityRuleManager.loadAuthorityConf (AuthorityRuleManager.java:105-136): the first valid rule of a resource
+        Map<String, AuthorityRule> kept = new HashMap<>();
+        for (AuthorityRule r : rules) {
+            if (AuthorityRuleManager.isValidRule(r)) {
+                kept.putIfAbsent(r.getResource(), r);
+            }
+        }
+        authorityByResource = kept;
+    }
+
+    static AuthorityRule authorityRule(String resource) {
+        return authorityByResource.get(resource);
     }
 
     static FlowRule flowRule(String resource, int slot) {

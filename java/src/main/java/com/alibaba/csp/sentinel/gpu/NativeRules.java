@@ -5,6 +5,7 @@ import java.lang.foreign.MemorySegment;
 import java.util.List;
 
 import com.alibaba.csp.sentinel.slots.block.ClusterRuleConstant;
+import com.alibaba.csp.sentinel.slots.block.authority.AuthorityRule;
 import com.alibaba.csp.sentinel.slots.block.degrade.DegradeRule;
 import com.alibaba.csp.sentinel.slots.block.flow.ClusterFlowConfig;
 import com.alibaba.csp.sentinel.slots.block.flow.FlowRule;
@@ -19,7 +20,7 @@ import static java.lang.foreign.ValueLayout.JAVA_LONG;
 
 /**
  * The rule beans as the C structs of sentinel_gpu.h (sg_flow_rule, sg_degrade_rule, sg_param_rule,
- * sg_param_item): field for field, with the beans' own defaults, strings as UTF-8 in the caller's arena.
+ * sg_param_item, sg_authority_rule): field for field, with the beans' own defaults, strings as UTF-8 in the caller's arena.
  * Offsets are those of SentinelGpu's layouts (checked against the C compiler by the tests).
  */
 final class NativeRules {
@@ -75,6 +76,21 @@ final class NativeRules {
             s.set(JAVA_DOUBLE, off(L, "count"), r.getCount());
             s.set(JAVA_INT, off(L, "time_window"), r.getTimeWindow());
             s.set(JAVA_INT, off(L, "grade"), r.getGrade());
+        }
+        return m;
+    }
+
+    /** AuthorityRule (core/slots/block/authority/AuthorityRule.java) -> sg_authority_rule[] */
+    static MemorySegment authority(Arena a, List<AuthorityRule> rules) {
+        final java.lang.foreign.StructLayout L = SentinelGpu.SG_AUTHORITY_RULE;
+        MemorySegment m = a.allocate(L, Math.max(1, rules.size()));
+        for (int i = 0; i < rules.size(); i++) {
+            AuthorityRule r = rules.get(i);
+            MemorySegment s = m.asSlice(i * L.byteSize(), L.byteSize());
+            s.set(ADDRESS, off(L, "resource"), str(a, r.getResource()));
+            s.set(ADDRESS, off(L, "limit_app"), str(a, r.getLimitApp()));
+            s.set(JAVA_INT, off(L, "strategy"), r.getStrategy());
+            s.set(JAVA_INT, off(L, "reserved"), 0);
         }
         return m;
     }

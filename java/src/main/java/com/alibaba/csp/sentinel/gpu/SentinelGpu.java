@@ -35,7 +35,8 @@ final class SentinelGpu {
     static final int MAX_ARGS = 24;
     static final long REF_NONE = 0xFFFFFFFFFFFFL;
     static final int PASS = 0, PASS_WAIT = 1, BLOCK_FLOW = 2, BLOCK_DEGRADE = 3, BLOCK_PARAM = 4, NO_CHECK = 5,
-        BLOCK_UPSTREAM = 6;
+        BLOCK_UPSTREAM = 6, BLOCK_AUTHORITY = 7;
+    static final int AUTHORITY_WHITE = 0, AUTHORITY_BLACK = 1;
 
     // ---- struct layouts (one member per line; see the class comment)
     static final StructLayout SG_CONFIG = MemoryLayout.structLayout(
@@ -89,6 +90,13 @@ final class SentinelGpu {
         JAVA_INT.withName("time_window"),
         JAVA_INT.withName("grade")
     ).withName("sg_degrade_rule");
+
+    static final StructLayout SG_AUTHORITY_RULE = MemoryLayout.structLayout(
+        ADDRESS.withName("resource"),
+        ADDRESS.withName("limit_app"),
+        JAVA_INT.withName("strategy"),
+        JAVA_INT.withName("reserved")
+    ).withName("sg_authority_rule");
 
     static final StructLayout SG_PARAM_ITEM = MemoryLayout.structLayout(
         ADDRESS.withName("object"),
@@ -196,6 +204,8 @@ final class SentinelGpu {
     static final MethodHandle LOAD_FLOW_RULES = fn("sg_load_flow_rules", rc(ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
     static final MethodHandle LOAD_DEGRADE_RULES = fn("sg_load_degrade_rules", rc(ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
     static final MethodHandle LOAD_PARAM_RULES = fn("sg_load_param_rules", rc(ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
+    static final MethodHandle LOAD_AUTHORITY_RULES = fn("sg_load_authority_rules",
+        rc(ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
     static final MethodHandle PARAM_KEY = fn("sg_param_key", rc(ADDRESS, ADDRESS, ADDRESS, ADDRESS));
     static final MethodHandle SUBMIT = fn("sg_submit", rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));
     static final MethodHandle SUBMIT_ASYNC = fn("sg_submit_async", rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));

@@ -32,6 +32,8 @@ CONTROL_BEHAVIOR_RATE_LIMITER = 2
 CONTROL_BEHAVIOR_WARM_UP_RATE_LIMITER = 3
 CLUSTER_THRESHOLD_AVG_LOCAL = 0
 CLUSTER_THRESHOLD_GLOBAL = 1
+AUTHORITY_WHITE = 0
+AUTHORITY_BLACK = 1
 
 EV_ENTRY = 0
 EV_EXIT = 1
@@ -53,6 +55,7 @@ BLOCK_DEGRADE = 3
 BLOCK_PARAM = 4
 NO_CHECK = 5
 BLOCK_UPSTREAM = 6
+BLOCK_AUTHORITY = 7
 NOT_ENTRY = 0xFF
 
 TOKEN_BAD_REQUEST = -4
@@ -134,6 +137,15 @@ class SgDegradeRule(C.Structure):
         ("count", C.c_double),
         ("time_window", C.c_int32),
         ("grade", C.c_int32),
+    ]
+
+
+class SgAuthorityRule(C.Structure):
+    _fields_ = [
+        ("resource", C.c_char_p),
+        ("limit_app", C.c_char_p),
+        ("strategy", C.c_int32),
+        ("reserved", C.c_int32),
     ]
 
 
@@ -333,6 +345,17 @@ def degrade_rule(resource, count, time_window, grade=DEGRADE_GRADE_RT, limit_app
     r.count = float(count)
     r.time_window = time_window
     r.grade = grade
+    return r
+
+
+def authority_rule(resource, limit_app, strategy=AUTHORITY_WHITE):
+    """An AuthorityRule (core/slots/block/authority/AuthorityRule.java): limit_app is a comma-separated list of
+    origin names, compared verbatim."""
+    r = SgAuthorityRule()
+    r.resource = resource.encode() if isinstance(resource, str) else resource
+    r.limit_app = limit_app.encode() if isinstance(limit_app, str) else limit_app
+    r.strategy = strategy
+    r.reserved = 0
     return r
 
 

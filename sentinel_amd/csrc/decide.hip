@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <stdint.h>
 
+#include "authority.h"
 #include "chain.h"
 #include "aux.h"
 #include "pmap.h"
@@ -953,7 +954,21 @@ __device__ int aux_check(const DevState& S, const DevCfg& cfg, const DRule& r, R
     return rc;
 }
 
-// One ENTRY through StatisticSlot -> ParamFlowSlot -> [caller's System/Authority] -> FlowSlot -> DegradeSlot
+// AuthoritySlot.checkBlackWhiteAuthority (core/slots/block/authority/AuthoritySlot.java:48-65): the resource's
+// authority rule blocks an entry from this origin.  Reads the table only when rules are loaded and the entry
+// names an origin; the intake sites (k_rs_first, k_grp_first, k_tiny) mark a resource PM_LANE with the same test.
+__device__ __forceinline__ bool authority_blocks(const DevState& S, uint32_t res, uint32_t origin_id) {
+    return S.auth != nullptr && origin_id != 0 && auth_blocks(S.auth, S.auth_ids, res, origin_id);
+}
+
+// The slots between ParamFlowSlot and FlowSlot (param/slots/HotParamSlotChainBuilder.java:38-51): the caller's
+// SystemSlot verdict (SG_F_BLOCKED_UPSTREAM) wins over the authority rule, as SystemSlot precedes AuthoritySlot.
+__device__ __forceinline__ uint32_t upstream_status(const DevState& S, uint32_t res, uint32_t fl, uint32_t origin_id) {
+    if (fl & SG_F_BLOCKED_UPSTREAM) return ST_BLOCK_UPSTREAM;
+    return authority_blocks(S, res, origin_id) ? ST_BLOCK_AUTHORITY : ST_PASS;
+}
+
+// One ENTRY through StatisticSlot -> ParamFlowSlot -> [caller's System] -> AuthoritySlot -> FlowSlot -> DegradeSlot
 // (param/slots/HotParamSlotChainBuilder.java:38-51, StatisticSlot.entry StatisticSlot.java:54-133).
 // rs[] is indexed only with unrolled constants, so for NRMAX <= 4 it stays in registers.  AUX: the
 // resource keeps origin nodes / DefaultNodes (k_lane<16> only).
@@ -966,6 +981,9 @@ __device__ __forceinline__ uint32_t lane_entry(Node& N, const Ctx& C, const DevS
     const bool aux = NRMAX >= 16;  // origin nodes / DefaultNodes (PM_AUX resources and PX_* rules are k_lane<16>'s)
     uint32_t status = ST_PASS, slot = 0;
     int64_t wait = 0;
+    // SystemSlot (the caller's flag), then AuthoritySlot: evaluated once (a pure function of the event), honoured
+    // after the param rules and before the first flow or degrade rule
+    const uint32_t up = upstream_status(S, res, fl, x.origin);
 #pragma unroll
     for (int s = 0; s < NRMAX; ++s) {
         if (s < nr && status == ST_PASS) {
@@ -1001,7 +1019,7 @@ __device__ __forceinline__ uint32_t lane_entry(Node& N, const Ctx& C, const DevS
                 if (!ok) { status = ST_BLOCK_PARAM; slot = r.slot; }
                 else wait += w;
             } else if (s < nfl) {  // FlowSlot.checkFlow (FlowSlot.java:146-158)
-                if (s == np && (fl & SG_F_BLOCKED_UPSTREAM)) { status = ST_BLOCK_UPSTREAM; slot = 0; continue; }
+                if (s == np && up != ST_PASS) { status = up; slot = 0; continue; }
                 const int sel = flow_select(r, x, rules + np, pg.n_flow, S.hot);
                 if (sel == SEL_NONE) continue;
                 int rc;
@@ -1017,11 +1035,12 @@ __device__ __forceinline__ uint32_t lane_entry(Node& N, const Ctx& C, const DevS
                 else if (rc == 2) { status = ST_PASS_WAIT; slot = r.slot; wait += w; }  // PriorityWaitException
                 else wait += w;
             } else {  // DegradeRuleManager.checkDegrade (DegradeRuleManager.java:72-85)
+                if (s == np && up != ST_PASS) { status = up; slot = 0; continue; }  // (no flow rule: still before DegradeSlot)
                 if (!degrade_pass(N, C, deg_param(r), rs[s], t)) { status = ST_BLOCK_DEGRADE; slot = r.slot; }
             }
         }
     }
-    if (status == ST_PASS && pg.n_flow == 0 && (fl & SG_F_BLOCKED_UPSTREAM)) { status = ST_BLOCK_UPSTREAM; slot = 0; }
+    if (status == ST_PASS && nr == np && up != ST_PASS) { status = up; slot = 0; }  // (no flow or degrade rule)
     // StatisticSlot.entry (StatisticSlot.java:54-133): DefaultNode -> ClusterNode, origin node
     const int what = status == ST_PASS ? 1 : status == ST_PASS_WAIT ? 2 : 0;
     if (aux) {  // ClusterBuilderSlot's origin node, NodeSelectorSlot's DefaultNode: counted whatever the rules
@@ -3807,6 +3826,8 @@ __global__ __launch_bounds__(TINY_MAX) void k_tiny(const sg_event* __restrict__ 
                 mark |= PM_AUX;
                 if (x.origin_id >> TAG_ORIGIN_BITS) mark |= PM_LANE;
             }
+            if (e.kind == SG_EV_ENTRY && e.res_id < max_res && authority_blocks(S, e.res_id, x.origin_id))
+                mark |= PM_LANE;  // (as k_rs_first)
         }
         if (own_args && e.kind == SG_EV_EXIT && (e.flags & SG_F_EXIT_ARGS)) mark |= PM_XARGS;
         if (e.kind == SG_EV_ENTRY) {

@@ -21,6 +21,8 @@
 
 namespace sg {
 
+struct AuthDesc;  // authority.h
+
 // one LeapArray bucket: MetricBucket (core/slots/statistic/data/MetricBucket.java:28-139)
 struct Bkt {
     int64_t ws;      // window start; -1 = never created (WindowWrap absent)
@@ -50,8 +52,8 @@ __host__ __device__ inline uint32_t ni_tm(uint32_t idx) { return 1u << (NI_TM_SH
 // segments to the per-lane kernel
 enum : uint8_t {
     PM_PRIO = 1,         // a prioritized ENTRY was seen: the second window's borrow ring is live
-    PM_LANE = 2,         // an event only k_lane implements was seen: SG_F_BLOCKED_UPSTREAM, a NullContext, an
-                         // origin id >= 2^20 (not packable into the record's node tag)
+    PM_LANE = 2,         // an event only k_lane implements was seen: SG_F_BLOCKED_UPSTREAM, an ENTRY its authority
+                         // rule blocks, a NullContext, an origin id >= 2^20 (not packable into the record's node tag)
     PM_AUX = 4,          // an event carried an origin or a named context: the resource keeps its origin
                          // StatisticNodes / context DefaultNodes whatever its rules are.  Rules that read them
                          // (PX_ORIGIN / PX_CHAIN) decide on k_lane<16>; otherwise the segment decides on its usual
@@ -227,7 +229,7 @@ static_assert(sizeof(PMap) == 64, "PMap must be 64 B");
 #define PQ_MAX_CAP 8176u       // largest map k_pq holds (its live-stamp ring of 2^15 bits in LDS: durationInSec <= 2)
 
 enum : uint8_t { ST_PASS = 0, ST_PASS_WAIT = 1, ST_BLOCK_FLOW = 2, ST_BLOCK_DEGRADE = 3, ST_BLOCK_PARAM = 4,
-                 ST_NO_CHECK = 5, ST_BLOCK_UPSTREAM = 6, ST_NOT_ENTRY = 0xFF };
+                 ST_NO_CHECK = 5, ST_BLOCK_UPSTREAM = 6, ST_BLOCK_AUTHORITY = 7, ST_NOT_ENTRY = 0xFF };
 
 #define HEAD_OFF 16384u  // DevCfg.dbg_flags: the cooperative owner decides XF_HEADT / XF_HEADR heads too (A/B)
 struct DevCfg {
@@ -450,6 +452,10 @@ struct DevState {
     uint32_t aux_cap;
     uint32_t max_ctx;         // context ids above this are NullContexts
     uint64_t aux_mask;
+    // AuthoritySlot on the device (authority.h): a descriptor per resource and the rules' origin ids; auth is null
+    // unless authority rules are loaded
+    const AuthDesc* auth;
+    const uint32_t* auth_ids;
 };
 
 enum : uint32_t { BF_PRIORITIZED = 1,

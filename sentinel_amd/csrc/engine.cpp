@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/sentinel_gpu.h"
+#include "authority.h"
 #include "dev_types.h"
 #include "pmap.h"  // (pm_buckets: sg_param_thread_count)
 
@@ -29,7 +30,8 @@ hipError_t launch_rs_first(const sg_event* ev, uint64_t n, uint32_t max_res, uin
                            uint64_t ring_mask, int32_t max_rt, SEv* rec_o, uint32_t* keys, uint32_t* vals,
                            uint32_t* ghist, uint32_t nblocks, uint32_t* bflags, int64_t* t0_out, uint32_t* prio,
                            uint64_t* key_ring, const uint32_t* comp, const sg_event_ext* ext, const sg_arg* args,
-                           uint64_t n_args, uint32_t max_ctx, hipStream_t st);
+                           uint64_t n_args, uint32_t max_ctx, const AuthDesc* auth, const uint32_t* auth_ids,
+                           hipStream_t st);
 // db = digit bits (8 or 10)
 hipError_t launch_radix_hist(const uint32_t* keys, uint64_t n, int shift, uint32_t* ghist, uint32_t nblocks,
                              hipStream_t st);
@@ -43,6 +45,7 @@ hipError_t launch_radix_scatter_x(const uint32_t* kin, const uint32_t* vin, uint
 hipError_t launch_grp_first(const sg_event* ev, uint64_t n, uint32_t max_res, uint64_t gbase, uint64_t ring_mask,
                             uint32_t* bflags, int64_t* t0_out, uint32_t* prio, uint64_t* key_ring, const uint32_t* comp,
                             const sg_event_ext* ext, const sg_arg* args, uint64_t n_args, uint32_t max_ctx,
+                            const AuthDesc* auth, const uint32_t* auth_ids,
                             const uint16_t* hot_tab, uint32_t nhot, uint32_t nblocks, uint32_t* words,
                             uint32_t* hot_hist, uint32_t* ckeys, uint32_t* cvals, uint32_t* ccnt, uint32_t* chist,
                             hipStream_t st);
@@ -629,6 +632,14 @@ struct sg_engine {
     // ContextUtil names: origins (0 = "") and contexts (0 = sentinel_default_context), first-intern order
     std::unordered_map<std::string, uint32_t> origin_ids, context_ids;
     std::unordered_map<std::string, int> rule_names;  // limitApp / CHAIN ref strings the flow rules name
+    // AuthorityRuleManager (authority.h): the kept rules, their device table ([max_resources] descriptors, allocated
+    // by the first non-empty load) and id lists; auth_on: rules are loaded (the kernels get null pointers otherwise)
+    AuthTable auth;
+    AuthDesc* d_auth = nullptr;
+    uint32_t* d_auth_ids = nullptr;
+    size_t auth_ids_cap = 0;
+    bool auth_on = false, auth_loaded = false;
+    std::vector<std::string> last_auth;
     uint32_t* d_comp = nullptr;  // [res] STRATEGY_RELATE component representative (sort key); null: none
     uint32_t* d_prev = nullptr;
     uint32_t* d_bsmall = nullptr;
@@ -860,6 +871,10 @@ static int collect(sg_engine* e, int k) {
     return SG_OK;
 }
 // every batch in flight done (called by the API functions that read or write engine state)
+// the authority table the kernels read: null unless authority rules are loaded (the kernels then run as without)
+static inline const AuthDesc* dev_auth(const sg_engine* e) { return e->auth_on ? e->d_auth : nullptr; }
+static inline const uint32_t* dev_auth_ids(const sg_engine* e) { return e->auth_on ? e->d_auth_ids : nullptr; }
+
 static int drain(sg_engine* e) {
     int rc = SG_OK;
     for (int i = 0; i < 2; ++i) {  // oldest first
@@ -1485,6 +1500,7 @@ int sg_engine_destroy(sg_engine* e) {
     dfree(e->d_pvseg); dfree(e->d_pvtseg); dfree(e->d_pvtot); dfree(e->d_pvrest);
     if (e->gstream) (void)hipStreamSynchronize(e->gstream);
     for (auto& B : e->slot) free_slot(B);
+    dfree(e->d_auth); dfree(e->d_auth_ids);
     dfree(e->d_prio); dfree(e->d_hot_tab); dfree(e->d_hot_list); dfree(e->d_hot_part); dfree(e->d_hot_hb); dfree(e->d_comp); dfree(e->d_auxtab); dfree(e->d_auxpool); dfree(e->d_auxcnt); dfree(e->d_auxmeta);
     dfree(e->d_pflow); dfree(e->d_phot); dfree(e->d_pftab); dfree(e->d_pvtab); dfree(e->d_preq); dfree(e->d_pvals);
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_nslimit); dfree(e->d_nsb); dfree(e->d_borrow); dfree(e->d_keyring);
@@ -1703,6 +1719,70 @@ int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint
     rc = rebuild_cluster(e, rules, n);
     if (rc) return rc;
     if (n_loaded) *n_loaded = (uint32_t)e->flows.size();
+    return SG_OK;
+}
+
+// AuthorityRuleManager.loadRules (core/slots/block/authority/AuthorityRuleManager.java:105-157); the rules are
+// compiled by authority.h.  Origins are not interned here (ids are dense in first-intern order): a listed name
+// without an id matches no event until sg_intern_origin gives it one and patches the lists.
+static int upload_authority(sg_engine* e) {
+    e->auth_on = false;
+    if (e->auth.empty()) return SG_OK;
+    const size_t R = e->cfg.max_resources;
+    if (!e->d_auth && hipMalloc(&e->d_auth, R * sizeof(AuthDesc)) != hipSuccess)
+        return fail(SG_ENOMEM, "device allocation of the authority table failed");
+    const size_t ni = std::max<size_t>(1, e->auth.ids.size());
+    if (ni > e->auth_ids_cap) {
+        if (e->d_auth_ids) (void)hipFree(e->d_auth_ids);
+        e->d_auth_ids = nullptr;
+        e->auth_ids_cap = 0;
+        if (hipMalloc(&e->d_auth_ids, 2 * ni * sizeof(uint32_t)) != hipSuccess)
+            return fail(SG_ENOMEM, "device allocation of the authority id lists failed");
+        e->auth_ids_cap = 2 * ni;
+    }
+    HIPCHK(hipMemcpy(e->d_auth, e->auth.desc.data(), R * sizeof(AuthDesc), hipMemcpyHostToDevice));
+    if (!e->auth.ids.empty())
+        HIPCHK(hipMemcpy(e->d_auth_ids, e->auth.ids.data(), e->auth.ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    e->auth_on = true;
+    return SG_OK;
+}
+
+int sg_load_authority_rules(sg_engine* e, const sg_authority_rule* rules, uint32_t n, uint32_t* n_loaded) {
+    if (!e || (n && !rules)) return fail(SG_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = drain(e)) return rc;  // no batch in flight while the table changes
+    std::vector<std::string> keys(n);
+    std::vector<AuthIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const sg_authority_rule& r = rules[i];
+        keys[i] = std::string(r.resource ? "r" : "R") + (r.resource ? r.resource : "") + '\x01' + (r.limit_app ? "l" : "L") +
+                  (r.limit_app ? r.limit_app : "") + '\x01' + std::to_string(r.strategy);
+        in[i] = AuthIn{r.resource, r.limit_app, r.strategy};
+    }
+    if (e->auth_loaded && keys == e->last_auth) {  // DynamicSentinelProperty.updateValue: an equal list is a no-op
+        if (n_loaded) *n_loaded = (uint32_t)e->auth.rules.size();
+        return SG_OK;
+    }
+    AuthTable old = e->auth;
+    int rrc = SG_OK;
+    const bool ok = e->auth.compile(
+        in.data(), n, e->cfg.max_resources,
+        [&](const char* name, uint32_t* id) { rrc = register_rule_resource(e, name, id); return rrc == SG_OK; },
+        [&](const char* name, uint32_t* id) {
+            auto it = e->origin_ids.find(name);
+            if (it == e->origin_ids.end()) return false;
+            *id = it->second;
+            return true;
+        });
+    if (!ok) return rrc;
+    if (int rc = upload_authority(e)) {
+        e->auth = std::move(old);
+        (void)upload_authority(e);
+        return rc;
+    }
+    e->last_auth = keys;
+    e->auth_loaded = true;
+    if (n_loaded) *n_loaded = (uint32_t)e->auth.rules.size();
     return SG_OK;
 }
 
@@ -2350,7 +2430,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     if (B.radix) {
         HIPCHK(launch_rs_first(dev_ev, n, R, e->gbase, e->d_ring, ring_mask, e->cfg.statistic_max_rt, e->d_rec_o,
                                e->d_k1, e->d_v1, e->d_hist, nblocks, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
-                               e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, gs));
+                               e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e), gs));
         for (int p = 0; p < passes; ++p) {
             if (p > 0) HIPCHK(launch_radix_hist(kin, n, p * db, e->d_hist, nblocks, gs));
             HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks << db, e->d_part, nullptr, gs));
@@ -2372,7 +2452,8 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         uint32_t* hot_off = e->d_pos;   // [hot id][tile] counts, scanned in place: the runs' sorted positions
         uint32_t* ccnt = B.d_ccnt;      // per tile: cold events (compacted at the tile's start in k1 / v1)
         HIPCHK(launch_grp_first(dev_ev, n, R, e->gbase, ring_mask, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
-                                e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, e->d_hot_tab, nhot, nblocks,
+                                e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e),
+                                e->d_hot_tab, nhot, nblocks,
                                 words, hot_off, e->d_k1, e->d_v1, ccnt, e->d_hist, gs));
         HIPCHK(launch_hot_scan(hot_off, nblocks, nhot, e->d_hot_part, e->d_hot_hb, e->d_bsmall + 77, gs));
         HIPCHK(launch_cold_n(n, e->d_bsmall + 77, e->d_bsmall + 78, gs));
@@ -2511,6 +2592,8 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     S.aux_cap = e->cfg.aux_node_capacity;
     S.aux_mask = e->aux_mask;
     S.max_ctx = SG_MAX_CONTEXTS;
+    S.auth = dev_auth(e);
+    S.auth_ids = dev_auth_ids(e);
     // ---- decide stage, in order after the previous batch's: references into earlier batches first
     HIPCHK(hipStreamWaitEvent(st, B.ev[1], 0));
     const uint32_t n_mix = e->has_mix ? head[6] : 0u, n_mixw = e->has_mix ? head[7] : 0u;
@@ -2806,6 +2889,8 @@ static int tiny_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext, 
     S.epoch = e->epoch; S.skip_ok = 0; S.skip_min = e->skip_min; S.ext = dev_ext; S.args = dev_args;
     S.aux_tab = e->d_auxtab; S.aux_count = e->d_auxcnt; S.aux_cap = e->cfg.aux_node_capacity; S.aux_mask = e->aux_mask;
     S.max_ctx = SG_MAX_CONTEXTS;
+    S.auth = dev_auth(e);
+    S.auth_ids = dev_auth_ids(e);
     // the chain grants: every one in place (no cap), none (a cap reached: CtSph.lookProcessChain then returns null),
     // or the host's, in first-ENTRY order (the batched path)
     const int cap = e->cfg.max_slot_chain_size;
@@ -2878,6 +2963,11 @@ int sg_intern_origin(sg_engine* e, const char* origin, uint32_t* out_id) {
     if (id >= 0x7FFFFFFFu) return fail(SG_ECAPACITY, "too many origins");
     e->origin_ids.emplace(origin, id);
     *out_id = id;
+    if (e->auth.by_name.count(origin)) {  // an authority rule lists the name: its id joins the rules' lists
+        if (int rc = drain(e)) return rc;
+        e->auth.on_intern(origin, id);
+        if (int rc = upload_authority(e)) return rc;
+    }
     if (e->rule_names.count(std::string("o\x01") + origin)) {
         if (int rc = drain(e)) return rc;
         return upload_rules(e, false, false, false);

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "../../include/sentinel_gpu.h"
+#include "authority.h"
 #include "dev_types.h"
 
 using namespace sg;
@@ -61,7 +62,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_first(const sg_event* __restr
                                                       const uint32_t* __restrict__ comp,
                                                       const sg_event_ext* __restrict__ ext,
                                                       const sg_arg* __restrict__ args, uint64_t n_args,
-                                                      uint32_t max_ctx) {
+                                                      uint32_t max_ctx, const AuthDesc* __restrict__ auth,
+                                                      const uint32_t* __restrict__ auth_ids) {
     constexpr int NB = 1 << DB;
     __shared__ uint32_t h[NB];
     for (int i = threadIdx.x; i < NB; i += RS_THREADS) h[i] = 0;
@@ -120,6 +122,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_first(const sg_event* __restr
                 if (x.origin_id >> TAG_ORIGIN_BITS) mark |= PM_LANE;  // not packable: k_lane reads the ext itself
                 else tag = x.origin_id | (x.context_id << TAG_ORIGIN_BITS);
             }
+            // an ENTRY its resource's authority rule blocks is k_lane's, as an upstream block is (auth: null
+            // unless authority rules are loaded)
+            if (auth && e.kind == SG_EV_ENTRY && x.origin_id != 0 && e.res_id < max_res &&
+                auth_blocks(auth, auth_ids, e.res_id, x.origin_id))
+                mark |= PM_LANE;
         }
         if (own_args) {  // the record's HAS_ARG: args[0] is a scalar (a k_pq check / thread-count key)
             r.flags = (uint8_t)((r.flags & ~SG_F_HAS_ARG) | (key0 != NO_KEY ? SG_F_HAS_ARG : 0));
@@ -207,6 +214,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_grp_first(const sg_event* __rest
                                                        uint64_t* __restrict__ key_ring, const uint32_t* __restrict__ comp,
                                                        const sg_event_ext* __restrict__ ext, const sg_arg* __restrict__ args,
                                                        uint64_t n_args, uint32_t max_ctx,
+                                                       const AuthDesc* __restrict__ auth,
+                                                       const uint32_t* __restrict__ auth_ids,
                                                        const uint16_t* __restrict__ hot_tab, uint32_t nhot,
                                                        uint32_t nblocks, uint32_t* __restrict__ words,
                                                        uint32_t* __restrict__ hot_hist, uint32_t* __restrict__ ckeys,
@@ -266,6 +275,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_grp_first(const sg_event* __rest
                     mark |= PM_AUX;
                     if (x.origin_id >> TAG_ORIGIN_BITS) mark |= PM_LANE;
                 }
+                if (auth && e.kind == SG_EV_ENTRY && x.origin_id != 0 && e.res_id < max_res &&
+                    auth_blocks(auth, auth_ids, e.res_id, x.origin_id))
+                    mark |= PM_LANE;  // (as k_rs_first)
             }
             if (own_args && e.kind == SG_EV_EXIT && (e.flags & SG_F_EXIT_ARGS)) mark |= PM_XARGS;
             if (e.kind == SG_EV_ENTRY) {
@@ -1096,10 +1108,11 @@ hipError_t launch_rs_first(const sg_event* ev, uint64_t n, uint32_t max_res, uin
                            uint64_t ring_mask, int32_t max_rt, SEv* rec_o, uint32_t* keys, uint32_t* vals,
                            uint32_t* ghist, uint32_t nblocks, uint32_t* bflags, int64_t* t0_out, uint32_t* prio,
                            uint64_t* key_ring, const uint32_t* comp, const sg_event_ext* ext, const sg_arg* args,
-                           uint64_t n_args, uint32_t max_ctx, hipStream_t st) {
+                           uint64_t n_args, uint32_t max_ctx, const AuthDesc* auth, const uint32_t* auth_ids,
+                           hipStream_t st) {
     hipLaunchKernelGGL(k_rs_first<8>, dim3(nblocks), dim3(RS_THREADS), 0, st, ev, n, max_res, gbase, ring, ring_mask,
                        max_rt, rec_o, keys, vals, ghist, nblocks, bflags, t0_out, prio, key_ring, comp, ext, args,
-                       n_args, max_ctx);
+                       n_args, max_ctx, auth, auth_ids);
     return hipGetLastError();
 }
 hipError_t launch_radix_hist(const uint32_t* keys, uint64_t n, int shift, uint32_t* ghist, uint32_t nblocks,
@@ -1139,12 +1152,13 @@ hipError_t launch_radix_scatter_x(const uint32_t* kin, const uint32_t* vin, uint
 hipError_t launch_grp_first(const sg_event* ev, uint64_t n, uint32_t max_res, uint64_t gbase, uint64_t ring_mask,
                             uint32_t* bflags, int64_t* t0_out, uint32_t* prio, uint64_t* key_ring, const uint32_t* comp,
                             const sg_event_ext* ext, const sg_arg* args, uint64_t n_args, uint32_t max_ctx,
+                            const AuthDesc* auth, const uint32_t* auth_ids,
                             const uint16_t* hot_tab, uint32_t nhot, uint32_t nblocks, uint32_t* words,
                             uint32_t* hot_hist, uint32_t* ckeys, uint32_t* cvals, uint32_t* ccnt, uint32_t* chist,
                             hipStream_t st) {
     hipLaunchKernelGGL(k_grp_first<8>, dim3(nblocks), dim3(RS_THREADS), 0, st, ev, n, max_res, gbase, ring_mask, bflags,
-                       t0_out, prio, key_ring, comp, ext, args, n_args, max_ctx, hot_tab, nhot, nblocks, words, hot_hist,
-                       ckeys, cvals, ccnt, chist);
+                       t0_out, prio, key_ring, comp, ext, args, n_args, max_ctx, auth, auth_ids, hot_tab, nhot, nblocks, words,
+                       hot_hist, ckeys, cvals, ccnt, chist);
     return hipGetLastError();
 }
 hipError_t launch_hot_scan(uint32_t* C, uint32_t nblocks, uint32_t nhot, uint32_t* part, uint32_t* hb, uint32_t* total,

@@ -26,7 +26,7 @@ EXPORTS = (
     "sg_cluster_request_tokens", "sg_cluster_request_param_tokens", "sg_read_node", "sg_last_error", "sg_last_timings",
     "sg_submit_ex", "sg_submit_ex_async", "sg_intern_origin", "sg_intern_context", "sg_param_thread_count",
     "sg_cluster_namespace", "sg_cluster_assign_flows", "sg_cluster_set_namespace_connected",
-    "sg_cluster_namespace_qps",
+    "sg_cluster_namespace_qps", "sg_load_authority_rules",
 )
 
 
@@ -51,6 +51,7 @@ def lib():
         L.sg_load_flow_rules.argtypes = [P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.sg_load_degrade_rules.argtypes = [P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.sg_load_param_rules.argtypes = [P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.sg_load_authority_rules.argtypes = [P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.sg_param_key.argtypes = [P, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
         L.sg_submit.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p]
         L.sg_submit_async.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -151,6 +152,10 @@ class Engine:
 
     def load_param_rules(self, rules) -> int:
         return self._load(lib().sg_load_param_rules, rules, A.SgParamRule)
+
+    def load_authority_rules(self, rules) -> int:
+        """AuthorityRuleManager.loadRules: A.authority_rule(...) list (empty: clear); returns the rules kept."""
+        return self._load(lib().sg_load_authority_rules, rules, A.SgAuthorityRule)
 
     # ---- decisions
     def submit(self, events: np.ndarray) -> np.ndarray:
