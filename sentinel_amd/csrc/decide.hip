@@ -168,7 +168,10 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
                                                  uint32_t* __restrict__ ashort, uint64_t* __restrict__ along,
                                                  uint64_t* __restrict__ amulti, uint32_t* __restrict__ mixc,
                                                  uint32_t* __restrict__ mix, uint32_t mix_cap,
-                                                 uint32_t* __restrict__ mixlen, uint32_t mix_wide, uint32_t head_min) {
+                                                 uint32_t* __restrict__ mixlen, uint32_t mix_wide, uint32_t head_min,
+                                                 const uint16_t* __restrict__ hot_tab, uint32_t nhot,
+                                                 const uint32_t* __restrict__ nhotseg, uint32_t* __restrict__ need_hot,
+                                                 uint32_t* __restrict__ need_blk) {
     __shared__ uint32_t cnt[N_BINS];
     for (uint32_t b = threadIdx.x; b < N_BINS; b += blockDim.x) cnt[b] = 0;
     __syncthreads();
@@ -233,6 +236,24 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
         const uint32_t rank = atomicAdd(&cnt[bin], 1u);
         sg.bin = bin | (auxp ? SEG_AUXP : 0u) | (rank << 8);
         segs[s] = sg;
+        // Side tables (forward links, bst[]) are read by the owners that skip frozen stretches only: k_grp_records and
+        // k_block_sums, which run after this kernel, build them for the segments marked here.  A hot segment
+        // (segs[0 .. *nhotseg)) marks its hot id, a cold one the 1024-position blocks it touches (whole words of 32
+        // blocks where it spans them); a marked block gets the tables of all its positions, its neighbours' included.
+        if (need_blk && (bin == BIN_J4 || bin == BIN_J8 || bin == BIN_J16) && sg.len) {
+            if (s < *nhotseg) {
+                const uint32_t hid = hot_tab[sg.res];
+                if (hid < nhot) need_hot[hid] = 1u;
+            } else {
+                const uint32_t b0 = sg.start >> 10, b1 = (sg.start + sg.len - 1) >> 10;
+                for (uint32_t wd = b0 >> 5; wd <= (b1 >> 5); ++wd) {
+                    uint32_t m32 = 0xFFFFFFFFu;
+                    if (wd == (b0 >> 5)) m32 &= 0xFFFFFFFFu << (b0 & 31);
+                    if (wd == (b1 >> 5)) m32 &= 0xFFFFFFFFu >> (31 - (b1 & 31));
+                    atomicOr(&need_blk[wd], m32);
+                }
+            }
+        }
     }
     if (aux) {  // (wave-uniform: every lane of the wave takes part)
         const uint32_t o = wave_alloc(aux + 0, aux_short ? 1u : 0u);
@@ -314,12 +335,18 @@ __global__ __launch_bounds__(256) void k_scatter_rec(const SEv* __restrict__ rec
 // STRATEGY_RELATE component the key is the component's).
 // skeys: the sorted keys of positions >= *lo (the hot / cold group stage's cold region: k_grp_records checked the
 // references of hot events; lo = null: every position, the radix group stage)
+// need_blk: the blocks whose tables have a reader (k_seg_bin; null: every block).  BF_MULTI_LINK is therefore raised
+// for a doubly named ENTRY inside a marked block only, which is all S.skip_ok protects.
 __global__ __launch_bounds__(256) void k_block_sums(const SEv* __restrict__ recs, const uint32_t* __restrict__ skeys,
                                                     uint64_t n, uint32_t* __restrict__ bst, Link* __restrict__ link,
                                                     uint32_t epoch, uint32_t* __restrict__ bflags,
-                                                    const uint32_t* __restrict__ lo) {
+                                                    const uint32_t* __restrict__ lo,
+                                                    const uint32_t* __restrict__ need_blk) {
     const uint32_t kmin = lo ? *lo : 0u;
     if ((uint64_t)(blockIdx.x + 1) * 1024 <= kmin) return;  // (the hot region: k_grp_records)
+    // need_blk (optional): one bit per block, set by k_seg_bin where a segment of a skipping owner touches the block;
+    // the other blocks' tables have no reader: their references are checked, no link is exchanged, nothing summed
+    const bool tables = !need_blk || ((need_blk[blockIdx.x >> 5] >> (blockIdx.x & 31)) & 1u);
     __shared__ uint32_t wsum[4];
     const uint64_t base = (uint64_t)blockIdx.x * 1024;
     // the four records as whole 16-byte loads (x = dt, y = x, z = cnt | rt << 16, w = kind | flags << 8 | code << 16),
@@ -346,7 +373,8 @@ __global__ __launch_bounds__(256) void k_block_sums(const SEv* __restrict__ recs
         const uint64_t p = base + (uint64_t)k * 256 + threadIdx.x;
         return xd[k] ? (uint32_t)(atomicExch(xd[k], ((unsigned long long)epoch << 32) | (uint32_t)p) >> 32) : 0u;
     };
-    const uint32_t o0 = xch(0), o1 = xch(1), o2 = xch(2), o3 = xch(3);
+    uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+    if (tables) { o0 = xch(0); o1 = xch(1); o2 = xch(2); o3 = xch(3); }  // (block-uniform)
     // a cold reference to a cold ENTRY: the same sort key (both keys loaded for every item, clamped)
     uint32_t ka[4], kb[4];
 #pragma unroll
@@ -362,6 +390,7 @@ __global__ __launch_bounds__(256) void k_block_sums(const SEv* __restrict__ recs
     const bool multi = o0 == epoch || o1 == epoch || o2 == epoch || o3 == epoch;  // (epochs start at 1)
     if (__ballot(multi) && (threadIdx.x & 63) == 0) atomicOr(bflags, BF_MULTI_LINK);
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(bflags, BF_BAD_REF);
+    if (!tables) return;
     for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -4026,9 +4055,9 @@ hipError_t launch_seg_cold(const uint32_t* keys, uint64_t n, const uint32_t* lo,
 }
 // the sorted-order side tables (bst sums, forward links) of the hot / cold group stage (its records are in place)
 hipError_t launch_block_sums(const SEv* recs, uint64_t n, uint32_t* bst, Link* link, uint32_t epoch, uint32_t* bflags,
-                             const uint32_t* skeys, const uint32_t* lo, hipStream_t st) {
+                             const uint32_t* skeys, const uint32_t* lo, const uint32_t* need_blk, hipStream_t st) {
     hipLaunchKernelGGL(k_block_sums, dim3((uint32_t)((n + 1023) / 1024)), dim3(256), 0, st, recs, skeys, n, bst, link,
-                       epoch, bflags, lo);
+                       epoch, bflags, lo, need_blk);
     return hipGetLastError();
 }
 // mp: the segment count on the device; mb: an upper bound of it (the grid)
@@ -4036,12 +4065,13 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint32_t lane_max, uint32_t j1_max, uint32_t j4_max, uint32_t force_lane, uint32_t* blkcnt,
                           uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
-                          uint32_t mix_wide, uint32_t head_min, hipStream_t st) {
+                          uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
+                          const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, hipStream_t st) {
     const uint32_t nblk = (mb + 255) / 256;
     if (!nblk) return hipSuccess;
     hipLaunchKernelGGL(k_seg_bin, dim3(nblk), dim3(256), 0, st, segs, mp, n, prog, prio, lane_max, j1_max, j4_max, force_lane,
                        blkcnt, nblk, pq_ok, pq_wide, aux, ashort, along, amulti, mixc, mix, mix_cap, mixlen, mix_wide,
-                       head_min);
+                       head_min, hot_tab, nhot, nhotseg, need_hot, need_blk);
     return hipGetLastError();
 }
 // off = exclusive scan of blkcnt (bin-major); writes the per-bin offsets to bin_off[0..N_BINS]
@@ -4061,7 +4091,7 @@ hipError_t launch_gather(const SEv* rec_o, const uint32_t* vals, const uint32_t*
     hipLaunchKernelGGL(k_scatter_rec, dim3(nb), dim3(256), 0, st, rec_o, n, pos_of, recs, prev, nprev, link, bst,
                        epoch, bflags);
     hipLaunchKernelGGL(k_block_sums, dim3((uint32_t)((n + 1023) / 1024)), dim3(256), 0, st, recs, skeys, n, bst, link,
-                       epoch, bflags, (const uint32_t*)nullptr);
+                       epoch, bflags, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
     return hipGetLastError();
 }
 hipError_t launch_fill(const Span* spans, const uint32_t* nspan, uint32_t cap, const SEv* recs, const Prog* prog,

@@ -232,6 +232,7 @@ enum : uint8_t { ST_PASS = 0, ST_PASS_WAIT = 1, ST_BLOCK_FLOW = 2, ST_BLOCK_DEGR
                  ST_NO_CHECK = 5, ST_BLOCK_UPSTREAM = 6, ST_BLOCK_AUTHORITY = 7, ST_NOT_ENTRY = 0xFF };
 
 #define HEAD_OFF 16384u  // DevCfg.dbg_flags: the cooperative owner decides XF_HEADT / XF_HEADR heads too (A/B)
+#define TABLES_ALL 32768u  // SG_DEBUG_FLAGS: the hot / cold group stage builds the side tables for every position (A/B)
 struct DevCfg {
     int32_t max_rt;
     int32_t occupy_timeout;

@@ -55,7 +55,8 @@ hipError_t launch_grp_records(const sg_event* ev, uint64_t n, uint64_t gbase, ui
                               const uint32_t* words, const uint32_t* P, uint32_t nhot, uint32_t nblocks,
                               const uint32_t* hb, SEv* recs, uint32_t* svals, uint32_t* prev,
                               uint32_t* nprev, uint32_t* bst, uint32_t* bflags, const sg_event_ext* ext,
-                              const sg_arg* args, uint32_t max_ctx, Link* link, uint32_t epoch, hipStream_t st);
+                              const sg_arg* args, uint32_t max_ctx, Link* link, uint32_t epoch,
+                              const uint32_t* need_hot, const uint32_t* need_blk, hipStream_t st);
 hipError_t launch_hot_segs(const uint32_t* hb, uint32_t nhot, const uint32_t* hot_list, Seg* segs, uint32_t* out,
                            hipStream_t st);
 hipError_t launch_hot_build(const Seg* segs, const uint32_t* mp, uint32_t mb, uint32_t min_len, uint32_t max_res, uint16_t* hot_tab,
@@ -69,7 +70,7 @@ hipError_t launch_seg_cold(const uint32_t* keys, uint64_t n, const uint32_t* lo,
                            hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
                            uint32_t* part, uint32_t* ccount, uint32_t* nseg);
 hipError_t launch_block_sums(const SEv* recs, uint64_t n, uint32_t* bst, Link* link, uint32_t epoch, uint32_t* bflags,
-                             const uint32_t* skeys, const uint32_t* lo, hipStream_t st);
+                             const uint32_t* skeys, const uint32_t* lo, const uint32_t* need_blk, hipStream_t st);
 hipError_t launch_radix_scatter(const uint32_t* kin, const uint32_t* vin, uint64_t n, int shift, const uint32_t* goff,
                                 uint32_t nblocks, uint32_t* kout, uint32_t* vout, uint32_t* pos_of, hipStream_t st);
 uint32_t radix_tile();
@@ -87,8 +88,8 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint32_t lane_max, uint32_t j1_max, uint32_t j4_max, uint32_t force_lane, uint32_t* blkcnt,
                           uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
-                          uint32_t mix_wide, uint32_t head_min,
-                          hipStream_t st);
+                          uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
+                          const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, hipStream_t st);
 // aux.hip
 hipError_t launch_aux(const SEv* recs, const Seg* segs, const uint32_t* aux, const uint32_t* ashort,
                       const uint64_t* along, uint64_t* apiece, const uint64_t* amulti, const DevState& S, const DevCfg& cfg,
@@ -614,6 +615,10 @@ struct sg_engine {
     uint32_t nhot = 0;
     uint32_t* d_hot_part = nullptr;  // the hot scan's per-chunk partials ((max tiles / 64 + 2) x HOT_MAX words)
     uint32_t* d_hot_hb = nullptr;    // per hot id: first sorted position, total (2 x HOT_MAX words)
+    // which side tables (forward links, bst[]) the batch being grouped needs (k_seg_bin): one word per hot id, then
+    // one bit per 1024-position block of the cold region
+    uint32_t* d_need = nullptr;
+    uint64_t need_words = 0;
     bool radix_group = false;    // SG_DEBUG_FLAGS & 8192: the all-radix group stage (A/B)
     uint64_t radix_below = 1u << 18;  // SG_RADIX_BELOW: batches of fewer events take the radix group stage (the drop-in's
                                       // 65,536-event batches: 36 vs 30-32 M entries/s on the hot / cold one)
@@ -812,6 +817,9 @@ int ensure_batch(sg_engine* e, uint64_t n) {
     }
     dfree(e->d_hot_part);
     dfree(e->d_hot_hb);
+    dfree(e->d_need);
+    e->need_words = hot_max() + c / 32768 + 2;
+    HIPCHK(hipMalloc(&e->d_need, e->need_words * 4));
     HIPCHK(hipMalloc(&e->d_hot_part, (nblocks / 16 + 2) * hot_max() * 4));  // (HS_TC >= 16 tiles a chunk)
     HIPCHK(hipMalloc(&e->d_hot_hb, 2 * hot_max() * 4));
     for (auto& B : e->slot) {
@@ -1501,7 +1509,7 @@ int sg_engine_destroy(sg_engine* e) {
     if (e->gstream) (void)hipStreamSynchronize(e->gstream);
     for (auto& B : e->slot) free_slot(B);
     dfree(e->d_auth); dfree(e->d_auth_ids);
-    dfree(e->d_prio); dfree(e->d_hot_tab); dfree(e->d_hot_list); dfree(e->d_hot_part); dfree(e->d_hot_hb); dfree(e->d_comp); dfree(e->d_auxtab); dfree(e->d_auxpool); dfree(e->d_auxcnt); dfree(e->d_auxmeta);
+    dfree(e->d_prio); dfree(e->d_hot_tab); dfree(e->d_hot_list); dfree(e->d_hot_part); dfree(e->d_hot_hb); dfree(e->d_need); dfree(e->d_comp); dfree(e->d_auxtab); dfree(e->d_auxpool); dfree(e->d_auxcnt); dfree(e->d_auxmeta);
     dfree(e->d_pflow); dfree(e->d_phot); dfree(e->d_pftab); dfree(e->d_pvtab); dfree(e->d_preq); dfree(e->d_pvals);
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_nslimit); dfree(e->d_nsb); dfree(e->d_borrow); dfree(e->d_keyring);
     dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx); dfree(e->d_tbounds);
@@ -2427,6 +2435,44 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     // every event through the radix passes: SG_DEBUG_FLAGS & 8192 (A/B of the group stage), or a batch of 2^30 events
     // or more (the hot / cold stage's words hold a position in 30 bits)
     B.radix = e->radix_group || n >= (1ull << 30) || n < e->radix_below;
+    // bins + bin-ordered dispatch list (per-block counts -> scan -> placement), sized by an upper bound of
+    // the segment count so that the group stage needs one host round trip
+    const bool force_lane = !e->cfg.switch_on || (e->dbg_flags & 2);
+    const uint32_t mb = (uint32_t)std::min<uint64_t>(n, R);
+    const uint32_t nblk = (mb + 255) / 256;
+    // Bin thresholds by batch size: a full batch (C4: 2^25 events) keeps the decide stage busy with event
+    // throughput, and wider owners for shorter segments cost more than they save (measured); in a batch of
+    // fewer than SHARD_BATCH (6.3M) events -- one rank's shard of a multi-GPU step -- the longest owner chains bound it
+    // instead, so segments get wider owners sooner (tools/shard_rehearsal.sh: 8-way shards of C4, mean
+    // rank step 1.70 -> 1.33 ms, slowest 1.85 -> 1.73 ms).
+    uint32_t lane_max = e->lane_max, j1_max = e->j1_max, j4_max = e->j4_max;
+    // (below SHARD_BATCH events: an 8-way shard of a 2^25-event global batch is ~2^22; a 4-way shard's 2^23 runs
+    // faster with the full-batch bins: 4-way rehearsal 2.24 -> 1.79 ms per global batch)
+    if (!e->bins_pinned && n < SHARD_BATCH) {
+        lane_max = std::min<uint32_t>(lane_max, 128);
+        j1_max = std::min<uint32_t>(j1_max, 1024);
+        j4_max = std::min<uint32_t>(j4_max, 4096);
+    }
+    // need_hot / need_blk (the hot / cold stage; null: the side tables everywhere): the segments whose owner can skip
+    // frozen stretches mark their hot id / their cold blocks, and the record kernels, which run after the bins there,
+    // build forward links and bst[] for those only
+    auto bins = [&](uint32_t* need_hot, uint32_t* need_blk) -> int {
+        if (ext) {  // the aux.hip post-pass lists of this slot
+            if (int arc = ensure_aux(e, B, n)) return arc;
+        }
+        if (e->has_mix) {  // the XF_MIX lists of this slot
+            if (int mrc = ensure_mix(B, mb)) return mrc;
+        }
+        HIPCHK(launch_seg_bin(e->d_segs, e->d_bsmall + 1, mb, n, e->d_prog, e->d_prio, lane_max, j1_max, j4_max,
+                              force_lane ? 1 : 0, e->d_blkcnt, e->pq_on ? 1u : 0u, e->pq_wide, ext ? e->d_bsmall + 130 : nullptr,
+                              B.d_ashort, B.d_along, B.d_amulti, e->d_bsmall + 6, e->has_mix ? B.d_mix : nullptr,
+                              (uint32_t)B.mix_cap, e->d_bsmall + 72, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
+                              (e->dbg_flags & HEAD_OFF) ? 0u : e->head_min, e->d_hot_tab, e->nhot, e->d_bsmall + 80, need_hot,
+                              need_blk, gs));
+        HIPCHK(launch_scan(e->d_blkcnt, e->d_blkcnt, (uint64_t)nblk * N_BINS, e->d_part, nullptr, gs));
+        HIPCHK(launch_seg_order(e->d_segs, e->d_bsmall + 1, mb, e->d_blkcnt, e->d_order, e->d_bsmall + 8, gs));
+        return SG_OK;
+    };
     if (B.radix) {
         HIPCHK(launch_rs_first(dev_ev, n, R, e->gbase, e->d_ring, ring_mask, e->cfg.statistic_max_rt, e->d_rec_o,
                                e->d_k1, e->d_v1, e->d_hist, nblocks, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
@@ -2442,6 +2488,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         HIPCHK(launch_seg(kin, n, e->d_flag, e->d_pos, e->d_segs, gs, launch_scan, e->d_part, e->d_bsmall + 1));
         HIPCHK(launch_gather(e->d_rec_o, vin, kin, n, e->d_posof, e->d_recs, e->d_prev, e->d_bsmall + 3, e->d_link,
                              e->d_bst, e->epoch, e->d_bsmall + 0, gs));
+        if (int brc = bins(nullptr, nullptr)) return brc;
     } else {
         // ---- hot / cold group stage (kernels.hip k_grp_*): [77] hot_total (the cold region's start), [78] cold
         // events, [80] hot segments, [81] (hot_total again), [82] cold segments, [76] the next batch's hot ids
@@ -2478,42 +2525,22 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         HIPCHK(launch_seg_cold(kin, n, e->d_bsmall + 77, e->d_bsmall + 80, ccnt + sc, ccnt + 2 * sc, e->d_segs, gs,
                                launch_scan, e->d_part, e->d_bsmall + 82, e->d_bsmall + 1));
         HIPCHK(hipMemsetAsync(e->d_bst, 0, ((n + 1023) / 1024) * 4, gs));
+        // the bins first: they read only the segments, the programs and the marks of k_grp_first, and say which
+        // side tables the record kernels must build (SG_DEBUG_FLAGS & 32768: all of them, as the radix stage does)
+        uint32_t *need_hot = nullptr, *need_blk = nullptr;
+        if (!(e->dbg_flags & TABLES_ALL)) {
+            need_hot = e->d_need;
+            need_blk = e->d_need + hot_max();
+            HIPCHK(hipMemsetAsync(e->d_need, 0, e->need_words * 4, gs));
+        }
+        if (int brc = bins(need_hot, need_blk)) return brc;
         HIPCHK(launch_grp_records(dev_ev, n, e->gbase, ring_mask, e->cfg.statistic_max_rt, words, hot_off, nhot, nblocks,
                                   e->d_hot_hb, e->d_recs, vin, e->d_prev, e->d_bsmall + 3, e->d_bst,
-                                  e->d_bsmall + 0, dev_ext, dev_args, SG_MAX_CONTEXTS, e->d_link, e->epoch, gs));
-        HIPCHK(launch_block_sums(e->d_recs, n, e->d_bst, e->d_link, e->epoch, e->d_bsmall + 0, kin, e->d_bsmall + 77, gs));
+                                  e->d_bsmall + 0, dev_ext, dev_args, SG_MAX_CONTEXTS, e->d_link, e->epoch, need_hot,
+                                  need_blk, gs));
+        HIPCHK(launch_block_sums(e->d_recs, n, e->d_bst, e->d_link, e->epoch, e->d_bsmall + 0, kin, e->d_bsmall + 77,
+                                 need_blk, gs));
     }
-    // bins + bin-ordered dispatch list (per-block counts -> scan -> placement), sized by an upper bound of
-    // the segment count so that the group stage needs one host round trip
-    const bool force_lane = !e->cfg.switch_on || (e->dbg_flags & 2);
-    const uint32_t mb = (uint32_t)std::min<uint64_t>(n, R);
-    const uint32_t nblk = (mb + 255) / 256;
-    // Bin thresholds by batch size: a full batch (C4: 2^25 events) keeps the decide stage busy with event
-    // throughput, and wider owners for shorter segments cost more than they save (measured); in a batch of
-    // fewer than SHARD_BATCH (6.3M) events -- one rank's shard of a multi-GPU step -- the longest owner chains bound it
-    // instead, so segments get wider owners sooner (tools/shard_rehearsal.sh: 8-way shards of C4, mean
-    // rank step 1.70 -> 1.33 ms, slowest 1.85 -> 1.73 ms).
-    uint32_t lane_max = e->lane_max, j1_max = e->j1_max, j4_max = e->j4_max;
-    // (below SHARD_BATCH events: an 8-way shard of a 2^25-event global batch is ~2^22; a 4-way shard's 2^23 runs
-    // faster with the full-batch bins: 4-way rehearsal 2.24 -> 1.79 ms per global batch)
-    if (!e->bins_pinned && n < SHARD_BATCH) {
-        lane_max = std::min<uint32_t>(lane_max, 128);
-        j1_max = std::min<uint32_t>(j1_max, 1024);
-        j4_max = std::min<uint32_t>(j4_max, 4096);
-    }
-    if (ext) {  // the aux.hip post-pass lists of this slot
-        if (int arc = ensure_aux(e, B, n)) return arc;
-    }
-    if (e->has_mix) {  // the XF_MIX lists of this slot
-        if (int mrc = ensure_mix(B, mb)) return mrc;
-    }
-    HIPCHK(launch_seg_bin(e->d_segs, e->d_bsmall + 1, mb, n, e->d_prog, e->d_prio, lane_max, j1_max, j4_max,
-                          force_lane ? 1 : 0, e->d_blkcnt, e->pq_on ? 1u : 0u, e->pq_wide, ext ? e->d_bsmall + 130 : nullptr,
-                          B.d_ashort, B.d_along, B.d_amulti, e->d_bsmall + 6, e->has_mix ? B.d_mix : nullptr,
-                          (uint32_t)B.mix_cap, e->d_bsmall + 72, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
-                          (e->dbg_flags & HEAD_OFF) ? 0u : e->head_min, gs));
-    HIPCHK(launch_scan(e->d_blkcnt, e->d_blkcnt, (uint64_t)nblk * N_BINS, e->d_part, nullptr, gs));
-    HIPCHK(launch_seg_order(e->d_segs, e->d_bsmall + 1, mb, e->d_blkcnt, e->d_order, e->d_bsmall + 8, gs));
     // the next batch's hot ids: this batch's resources of >= n / 8192 events (about one per 4096-event tile, so
     // that a tile's run of one hot id is more than a random write), at least 64
     const uint32_t hot_min = (uint32_t)std::max<uint64_t>(64, n / 8192);

@@ -450,12 +450,15 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
                                                             uint32_t* __restrict__ bflags,
                                                             const sg_event_ext* __restrict__ ext,
                                                             const sg_arg* __restrict__ args, uint32_t max_ctx,
-                                                            Link* __restrict__ link, uint32_t epoch) {
+                                                            Link* __restrict__ link, uint32_t epoch,
+                                                            const uint32_t* __restrict__ need_hot,
+                                                            const uint32_t* __restrict__ need_blk) {
     __shared__ uint4 srec[GR_EVENTS];        // the quarter's hot records in (hot id, rank) order
     __shared__ uint32_t spos[GR_EVENTS], sval[GR_EVENTS];
     __shared__ uint32_t lo[HOT_MAX];         // per hot id: the quarter's count, then its first local slot
     __shared__ uint32_t r0[HOT_MAX];         // ... its first rank in the tile's run
     __shared__ uint32_t prow[HOT_MAX];       // ... the tile's run's first sorted position
+    __shared__ uint8_t hneed[HOT_MAX];       // ... its segment's owner can skip: it reads the side tables (k_seg_bin)
     __shared__ uint32_t ws[GR_THREADS / 64];
     __shared__ uint32_t nh_q;
     const uint32_t t = threadIdx.x, l = t & 63, wv = t >> 6;
@@ -478,6 +481,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
         lo[h] = 0;
         r0[h] = 0xFFFFFFFFu;
         prow[h] = P[(uint64_t)tile * nhot + h];
+        hneed[h] = (!need_hot || need_hot[h]) ? 1 : 0;  // (no marks: the tables everywhere)
     }
     __syncthreads();
 #pragma unroll
@@ -615,7 +619,9 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
                     r.x = (uint32_t)(ref & ring_mask);
                     is_prev = true;
                 }
-                if (r.code == RC_NONE || r.code == RC_PREV) atomicOr(&bst[q >> 10], BST_STATIC);
+                // (side tables where they have a reader only: a marked hot id, a marked cold block)
+                const bool tabs = hot ? hneed[hid] != 0 : (!need_blk || ((need_blk[q >> 15] >> ((q >> 10) & 31)) & 1u));
+                if ((r.code == RC_NONE || r.code == RC_PREV) && tabs) atomicOr(&bst[q >> 10], BST_STATIC);
             }
             uint4 rv;
             __builtin_memcpy(&rv, &r, sizeof(rv));
@@ -623,7 +629,8 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
                 const uint32_t slot = lo[hid] + (w & 0xFFFu) - r0[hid];
                 srec[slot] = rv;
                 spos[slot] = q;
-                sval[slot] = (uint32_t)i | (entry ? 0x80000000u : 0u);
+                // (bit 30, in LDS only: the id is marked; a batch of this stage has fewer than 2^30 events)
+                sval[slot] = (uint32_t)i | (entry ? 0x80000000u : 0u) | (hneed[hid] ? 0x40000000u : 0u);
             } else {
                 reinterpret_cast<uint4*>(recs)[q] = rv;
             }
@@ -644,7 +651,9 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
     // the hot runs leave in slot order: consecutive slots of one id are consecutive positions.  On the way, the
     // sorted-order side tables of the hot region (k_block_sums does the cold one): each 1024-position block's ENTRY
     // count sum (a segmented wave sum over equal blocks: a run's positions are consecutive) and the forward link of
-    // every referenced ENTRY (an EXIT run names an earlier tile's run of ENTRYs: nearby link slots).
+    // every referenced ENTRY (an EXIT run names an earlier tile's run of ENTRYs: nearby link slots).  Only the
+    // owners that skip frozen stretches read the tables, so only the hot ids k_seg_bin marked get them (need_hot;
+    // a cold event's BST_STATIC likewise by its block's bit in need_blk; null: every id and block).
     const uint32_t nh = nh_q;
     bool multi = false;
     for (uint32_t k0 = 0; k0 < nh; k0 += GR_THREADS) {  // (wave-uniform trip count)
@@ -654,10 +663,9 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
             const uint32_t q = spos[k];
             const uint4 rv = srec[k];
             reinterpret_cast<uint4*>(recs)[q] = rv;
-            svals[q] = sval[k];
+            svals[q] = sval[k] & ~0x40000000u;
             key = q >> 10;
-            const uint32_t kind = rv.w & 0xFFu, code = (rv.w >> 16) & 0xFFu;
-            if (kind == SG_EV_ENTRY) v = rv.z & 0xFFFFu;
+            if ((rv.w & 0xFFu) == SG_EV_ENTRY && (sval[k] & 0x40000000u)) v = rv.z & 0xFFFFu;
         }
         // segmented inclusive sum over runs of equal blocks; the last lane of each run adds it
         const uint32_t kp = __shfl_up(key, 1, 64), kn = __shfl_down(key, 1, 64);
@@ -685,7 +693,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
         if (k < nh) {
             const uint4 rv = srec[k];
             const uint32_t kind = rv.w & 0xFFu, code = (rv.w >> 16) & 0xFFu;
-            if (kind != SG_EV_ENTRY && code == RC_BATCH) {
+            if (kind != SG_EV_ENTRY && code == RC_BATCH && (sval[k] & 0x40000000u)) {
                 xd[it] = reinterpret_cast<unsigned long long*>(kind == SG_EV_EXIT ? &link[rv.y].exit_l
                                                                                   : &link[rv.y].trace_l);
                 xv[it] = ((unsigned long long)epoch << 32) | spos[k];
@@ -1174,9 +1182,11 @@ hipError_t launch_grp_records(const sg_event* ev, uint64_t n, uint64_t gbase, ui
                               const uint32_t* words, const uint32_t* P, uint32_t nhot, uint32_t nblocks,
                               const uint32_t* hb, SEv* recs, uint32_t* svals, uint32_t* prev,
                               uint32_t* nprev, uint32_t* bst, uint32_t* bflags, const sg_event_ext* ext,
-                              const sg_arg* args, uint32_t max_ctx, Link* link, uint32_t epoch, hipStream_t st) {
+                              const sg_arg* args, uint32_t max_ctx, Link* link, uint32_t epoch,
+                              const uint32_t* need_hot, const uint32_t* need_blk, hipStream_t st) {
     hipLaunchKernelGGL(k_grp_records, dim3(nblocks * 4), dim3(GR_THREADS), 0, st, ev, n, gbase, ring_mask, max_rt, words, P,
-                       nhot, nblocks, hb, recs, svals, prev, nprev, bst, bflags, ext, args, max_ctx, link, epoch);
+                       nhot, nblocks, hb, recs, svals, prev, nprev, bst, bflags, ext, args, max_ctx, link, epoch, need_hot,
+                       need_blk);
     return hipGetLastError();
 }
 hipError_t launch_hot_segs(const uint32_t* hb, uint32_t nhot, const uint32_t* hot_list, Seg* segs, uint32_t* out,
