@@ -1330,6 +1330,9 @@ struct LiteMin {
     Bkt fb;
 };
 __device__ __forceinline__ void md_zero(MinDelta& d) { d.p = d.b = d.s = d.rt = d.e = 0; d.minrt = INT32_MAX; }
+// A segment longer than that (SG_LANE_MAX, debug flag 2) with counts up to 65,535: the second's deltas go into its
+// bucket before one of them can pass 2^31 (each event adds at most 65,535 to a field; the same second rolls again)
+__device__ __forceinline__ bool md_full(const MinDelta& d) { return (uint32_t)(d.p | d.b | d.s | d.rt | d.e) >= 0x40000000u; }
 // LeapArray.currentWindow on the minute bucket of second T, then the second's additions
 __device__ __forceinline__ Bkt md_apply(Bkt b, int64_t T, const MinDelta& d, int32_t max_rt) {
     if (b.ws > T) return b;  // detached: the additions are lost (Q3)
@@ -1474,7 +1477,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
         if (kind == SG_EV_ENTRY) {
             if (!chain) d = mk_dec(ST_NO_CHECK, 0, 0);
             else {
-                if (T != L.T) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
+                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
                 uint32_t status = ST_PASS, slot = 0;
                 uint64_t key = NO_KEY;
                 if (PL) {  // ParamFlowSlot: initHotParamMetricsFor, the rule's index bit, then its check
@@ -1541,7 +1544,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
                 } else eff = st_passed(dec[rx] & 0xFF);  // written by this lane
             }
             if (eff && kind == SG_EV_EXIT) {  // StatisticSlot.exit
-                if (T != L.T) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
+                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
                 const int sl = sec_current(N, t, C.max_rt);
                 sec_add(N, sl, 0, 0, cntv, rtv, 0, rtv);
                 L.pd.s += cntv;
@@ -1561,7 +1564,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
                     }
                 }
             } else if (eff && cntv > 0) {  // ClusterNode.trace
-                if (T != L.T) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
+                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
                 const int sl = sec_current(N, t, C.max_rt);
                 sec_add(N, sl, 0, 0, 0, 0, cntv, INT64_MAX);
                 L.pd.e += cntv;
@@ -1615,6 +1618,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
 __device__ __forceinline__ uint32_t op_add(uint32_t a, uint32_t b) { return a + b; }
 __device__ __forceinline__ uint32_t op_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t op_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
+// A wave's total of per-lane u32 sums, in 64 bits (lane 63 holds it).  Counts and RTs go up to 65,535 an event, so the
+// lanes' sums of a long stretch add up past 2^32 within one wave; the halves are scanned apart (64 * 65,535 fits).
+__device__ __forceinline__ void wave_total64(uint32_t v, uint64_t* dst) {
+    uint32_t lo = v & 0xFFFFu, hi = v >> 16;
+    WAVE_SCAN(lo, 0u, op_add);
+    WAVE_SCAN(hi, 0u, op_add);
+    if (lane_id() == 63) *dst = (uint64_t)lo + ((uint64_t)hi << 16);
+}
 // segmented count: bit31 = "reset here", low bits = count since the last reset; a is the earlier element
 __device__ __forceinline__ uint32_t op_seg(uint32_t a, uint32_t b) {
     return (b & 0x80000000u) ? b : ((a & 0x80000000u) | ((a + b) & 0x7fffffffu));
@@ -1715,8 +1726,10 @@ struct JacSh {
     int64_t cP, cB, cS, cRT, cE, cTH;
     uint32_t cminrt, ctouch;
     uint32_t has_sync, warm_reach;
-    uint32_t c0, last_out, round_open, pad;
+    uint32_t c0, last_out, round_open;
+    uint32_t frz_stop;  // position at which a frozen stretch stopped without committing anything (NO_LANE: none)
     uint32_t part[NW][Q_TR + (MD + 1) / 2];
+    uint64_t part64[NW][5];  // stretch ends: the waves' pass / success / RT / exception / block unit totals
     uint32_t pseg[NW][MD];
     int64_t prl[NW][4];
     uint32_t mism[2][NW];
@@ -1942,6 +1955,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
         sh.round_open = 0;
         sh.c0 = 0;
         sh.last_out = (uint32_t)nr;
+        sh.frz_stop = NO_LANE;
         sh.npend = 0;
         sh.nsp = 0;
     }
@@ -2184,7 +2198,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
             for (int s = 0; s < MF; ++s)
                 if (s < nf) sat |= warmm ? fblock(s, Pfix, 1) : (double)j_iadd(pint, 1) > flim[s];
             sat = uni(sat) != 0;
-            if (sat || cutk0) {
+            // A stretch that stops at its first position commits nothing: an ENTRY acquiring 0 passes a saturated
+            // DefaultController (curCount + 0 > count is false, DefaultController.java:49-81).  The Jacobi iteration
+            // decides that position (sh.frz_stop); the stretch would otherwise be entered at it again and again.
+            if ((sat || cutk0) && uni(sh.frz_stop) != tbase + c0) {
                 constexpr uint32_t EPL = 4, ST = EPL * HW;  // events per lane, positions per super-tile
                 static_assert(WIN - ST >= (FULL_FENCE_TILES + 1) * (ST + HW), "old references must precede a full fence");
                 flush(tbase);     // the tile's committed decisions before the stretch
@@ -2475,15 +2492,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                         if (((warmm >> s) & 1) && __ballot((freach >> s) & 1) && lane == 0) atomicOr(&sh.warm_reach, 1u << s);
                 }
                 // stretch end: reduce the lane accumulators into the round's committed totals
-                WAVE_SCAN(aB, 0u, op_add);
-                WAVE_SCAN(aS, 0u, op_add);
-                WAVE_SCAN(aRT, 0u, op_add);
-                WAVE_SCAN(aE, 0u, op_add);
+                // (sh.part64: the leader's last read of it is behind a barrier every wave has passed)
+                wave_total64(aS, &sh.part64[wv][1]);
+                wave_total64(aRT, &sh.part64[wv][2]);
+                wave_total64(aE, &sh.part64[wv][3]);
+                wave_total64(aB, &sh.part64[wv][4]);
                 WAVE_SCAN(aTI, 0u, op_add);
                 WAVE_SCAN(aTH, 0u, op_add);
                 WAVE_SCAN(aMin, NO_LANE, op_min);
                 if (lane == 63) {
-                    sh.part[wv][0] = aB; sh.part[wv][1] = aS; sh.part[wv][2] = aRT; sh.part[wv][3] = aE;
                     sh.part[wv][4] = aTI; sh.part[wv][5] = aTH; sh.part[wv][6] = aMin;
                 }
                 // re-enter the tile machinery at the stop position; guesses = the frozen verdict
@@ -2504,12 +2521,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                 __syncthreads();
                 if (tid == 0) {
                     for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-                        sh.cB += sh.part[w][0]; sh.cS += sh.part[w][1]; sh.cRT += sh.part[w][2]; sh.cE += sh.part[w][3];
+                        sh.cB += (int64_t)sh.part64[w][4]; sh.cS += (int64_t)sh.part64[w][1];
+                        sh.cRT += (int64_t)sh.part64[w][2]; sh.cE += (int64_t)sh.part64[w][3];
                         sh.ctouch += sh.part[w][4]; sh.cTH += (int32_t)sh.part[w][5];
                         sh.cminrt = op_min(sh.cminrt, sh.part[w][6]);
                     }
                     sh.last_out = g;
                     sh.c0 = c0;
+                    if (fend == fpos0) sh.frz_stop = fend;  // (positions only grow: a stale one never matches again)
                 }
                 lds_barrier();
                 PROF_MARK(8)
@@ -2661,26 +2680,26 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                         for (int s = 0; s < MF; ++s)
                             if (((warmm >> s) & 1) && __ballot((freach >> s) & 1) && lane == 0) atomicOr(&sh.warm_reach, 1u << s);
                     }
-                    WAVE_SCAN(aP, 0u, op_add);
-                    WAVE_SCAN(aS, 0u, op_add);
-                    WAVE_SCAN(aRT, 0u, op_add);
-                    WAVE_SCAN(aE, 0u, op_add);
+                    wave_total64(aP, &sh.part64[wv][0]);  // (sh.part64: see the frozen stretch's end)
+                    wave_total64(aS, &sh.part64[wv][1]);
+                    wave_total64(aRT, &sh.part64[wv][2]);
+                    wave_total64(aE, &sh.part64[wv][3]);
+                    wave_total64(aB, &sh.part64[wv][4]);
                     WAVE_SCAN(aTI, 0u, op_add);
                     WAVE_SCAN(aTH, 0u, op_add);
                     WAVE_SCAN(aMin, NO_LANE, op_min);
-                    WAVE_SCAN(aB, 0u, op_add);
                     lds_barrier();  // every wave is past its reads of sh.part
                     if (lane == 63) {
-                        sh.part[wv][0] = aP; sh.part[wv][1] = aS; sh.part[wv][2] = aRT; sh.part[wv][3] = aE;
-                        sh.part[wv][4] = aTI; sh.part[wv][5] = aTH; sh.part[wv][6] = aMin; sh.part[wv][7] = aB;
+                        sh.part[wv][4] = aTI; sh.part[wv][5] = aTH; sh.part[wv][6] = aMin;
                     }
                     lds_barrier();
                     if (tid == 0) {
                         for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-                            sh.cP += sh.part[w][0]; sh.cS += sh.part[w][1]; sh.cRT += sh.part[w][2]; sh.cE += sh.part[w][3];
+                            sh.cP += (int64_t)sh.part64[w][0]; sh.cS += (int64_t)sh.part64[w][1];
+                            sh.cRT += (int64_t)sh.part64[w][2]; sh.cE += (int64_t)sh.part64[w][3];
                             sh.ctouch += sh.part[w][4]; sh.cTH += (int32_t)sh.part[w][5];
                             sh.cminrt = op_min(sh.cminrt, sh.part[w][6]);
-                            sh.cB += sh.part[w][7];
+                            sh.cB += (int64_t)sh.part64[w][4];
                         }
                         if (seg_pending) m_seg();
                     }
@@ -3138,18 +3157,17 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                     for (int s = 0; s < MF; ++s)
                         if (((warmm >> s) & 1) && __ballot((freach >> s) & 1) && lane == 0) atomicOr(&sh.warm_reach, 1u << s);
                 }
-                WAVE_SCAN(aP, 0u, op_add);
-                WAVE_SCAN(aS, 0u, op_add);
-                WAVE_SCAN(aRT, 0u, op_add);
-                WAVE_SCAN(aE, 0u, op_add);
+                wave_total64(aP, &sh.part64[wv][0]);
+                wave_total64(aS, &sh.part64[wv][1]);
+                wave_total64(aRT, &sh.part64[wv][2]);
+                wave_total64(aE, &sh.part64[wv][3]);
+                wave_total64(aB, &sh.part64[wv][4]);
                 WAVE_SCAN(aTI, 0u, op_add);
                 WAVE_SCAN(aTH, 0u, op_add);
                 WAVE_SCAN(aMin, NO_LANE, op_min);
-                WAVE_SCAN(aB, 0u, op_add);
                 lds_barrier();  // sh.part's chunk exchange is read; sh.os_* is written
                 if (lane == 63) {
-                    sh.part[wv][0] = aP; sh.part[wv][1] = aS; sh.part[wv][2] = aRT; sh.part[wv][3] = aE;
-                    sh.part[wv][4] = aTI; sh.part[wv][5] = aTH; sh.part[wv][6] = aMin; sh.part[wv][7] = aB;
+                    sh.part[wv][4] = aTI; sh.part[wv][5] = aTH; sh.part[wv][6] = aMin;
                 }
                 const uint32_t g = g_exit;
                 tbase = fend / TILE * TILE;
@@ -3168,10 +3186,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                 __syncthreads();
                 if (tid == 0) {
                     for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-                        sh.cP += sh.part[w][0]; sh.cS += sh.part[w][1]; sh.cRT += sh.part[w][2]; sh.cE += sh.part[w][3];
+                        sh.cP += (int64_t)sh.part64[w][0]; sh.cS += (int64_t)sh.part64[w][1];
+                        sh.cRT += (int64_t)sh.part64[w][2]; sh.cE += (int64_t)sh.part64[w][3];
                         sh.ctouch += sh.part[w][4]; sh.cTH += (int32_t)sh.part[w][5];
                         sh.cminrt = op_min(sh.cminrt, sh.part[w][6]);
-                        sh.cB += sh.part[w][7];
+                        sh.cB += (int64_t)sh.part64[w][4];
                     }
                     if (seg_pending) m_seg();
                     sh.last_out = g;

@@ -2453,6 +2453,12 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         j1_max = std::min<uint32_t>(j1_max, 1024);
         j4_max = std::min<uint32_t>(j4_max, 4096);
     }
+    // A cooperative owner's lanes sum a stretch's acquire units (<= 65,535 an event) in 32 bits before the 64-bit
+    // reduction at the stretch's end, so one owner of 64 * NW lanes takes at most 65,000 events a lane: a pinned limit
+    // above that hands the segment to the next wider owner.  (The 512-lane owner ends at J8_MAX = 2^23 events; the
+    // 1,024-lane one reaches its 66.5M only in a batch twice the default max_batch_events.)
+    j1_max = std::min<uint32_t>(j1_max, 64u * 65000u);
+    j4_max = std::min<uint32_t>(j4_max, 256u * 65000u);
     // need_hot / need_blk (the hot / cold stage; null: the side tables everywhere): the segments whose owner can skip
     // frozen stretches mark their hot id / their cold blocks, and the record kernels, which run after the bins there,
     // build forward links and bst[] for those only
