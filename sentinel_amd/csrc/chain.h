@@ -180,9 +180,10 @@ __device__ __forceinline__ void exc_advance(Node& N, const Bkt* minb, int64_t T)
         N.exc_sum = s;
     } else {
         // the seconds that fall out of the window (one bucket a round trip: issuing four at once measured slower in
-        // k_lite and k_jac<8>, profiles/r06 A/B)
+        // k_lite and k_jac<8>, profiles/r06 A/B).  The sum is one of non-negative bucket counts: once it is 0 no
+        // bucket still to fall out can subtract anything, so the walk ends there (and reads nothing at a sum of 0).
         const int64_t x1 = T - 60000;
-        for (int64_t x = N.exc_sum_sec - 59000; x <= x1; x += 1000) {
+        for (int64_t x = N.exc_sum_sec - 59000; x <= x1 && N.exc_sum != 0; x += 1000) {
             const int sl = (int)((x / 1000) % 60);
             const Bkt b = sl == N.pfslot ? N.pf : minb[sl];
             if (b.ws == x) N.exc_sum -= b.exc;

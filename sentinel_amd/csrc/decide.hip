@@ -1309,14 +1309,17 @@ __global__ __launch_bounds__(256) void k_lane(const SEv* __restrict__ recs, cons
 // rate-limiter / borrow code, so its code fits the instruction cache and its state fits in VGPRs.
 //
 // Minute window: a lite segment is a cold resource, a few events per second, so nearly every event
-// opens a new second and the read of that second's bucket (to tell "same second, accumulate" from
-// "stale slot, reset") would be an HBM round trip on every event's critical path.  No check of a lite
-// segment reads the current second's minute bucket (the flow checks read the second window, the
-// exception-count breaker a running sum of expired seconds), so the events of a second accumulate
-// into register deltas and the bucket is read-modified-written when the segment moves on: its load is
-// issued at that second change and consumed at the next one, off the critical path.  (A bucket with a
-// later window start -- the clock went back a minute -- would need the old path's "detached" drop;
-// that only happens in a batch rejected with BF_BACKWARD.)
+// opens a new second.  No check of a lite segment reads the current second's minute bucket (the flow
+// checks read the second window, the exception-count breaker a running sum of expired seconds), so
+// the events of a second accumulate into register deltas and the bucket is written when the segment
+// moves on.  LeapArray.currentWindow on that bucket either keeps it (same second), resets it (an older
+// second on the slot) or finds it detached (a later second: the clock went back); only the first and
+// the last need its contents.  Every writer of a minute bucket of second X also leaves the resource's
+// second window at a start >= X, except the metrics snapshot, whose seconds the host knows (DESIGN §5,
+// "k_lite: stale buckets are stored, not read").  So with H = the later of the second window's latest
+// start (rounded down to a second) and the highest snapshot second, a bucket of a second T > H holds an
+// older second and is stored whole, without a load; T <= H (the second the resource last wrote, or the
+// clock gone back) keeps the read-modify-write.  The lane's own writes raise H as it goes.
 // =================================================================================
 struct MinDelta {
     int32_t p, b, s, rt, e, minrt;  // per-second deltas of a cold resource (<= 256 events) fit in int32
@@ -1324,10 +1327,7 @@ struct MinDelta {
 struct LiteMin {
     int64_t T;      // second of the pending deltas (-1: none yet)
     MinDelta pd;    // pending deltas of second T
-    bool fly;       // an RMW in flight: bucket fb (loaded at the last second change) + deltas fd of second fT
-    int64_t fT;
-    MinDelta fd;
-    Bkt fb;
+    int64_t H;      // no minute bucket of this resource holds a second later than H
 };
 __device__ __forceinline__ void md_zero(MinDelta& d) { d.p = d.b = d.s = d.rt = d.e = 0; d.minrt = INT32_MAX; }
 // A segment longer than that (SG_LANE_MAX, debug flag 2) with counts up to 65,535: the second's deltas go into its
@@ -1341,29 +1341,43 @@ __device__ __forceinline__ Bkt md_apply(Bkt b, int64_t T, const MinDelta& d, int
     if ((int64_t)d.minrt < b.minrt) b.minrt = d.minrt;
     return b;
 }
-__device__ __forceinline__ void lm_finish(LiteMin& L, Bkt* minb, int32_t max_rt) {
-    if (L.fly) {
-        minb[(L.fT / 1000) % 60] = md_apply(L.fb, L.fT, L.fd, max_rt);
-        L.fly = false;
+// the pending second's bucket goes to HBM.  check (SG_LITE_CHECK): the stored-whole path reads the window start it
+// overwrites and reports a bucket that was not stale
+__device__ __forceinline__ void lm_put(LiteMin& L, Bkt* minb, int32_t max_rt, bool check, uint32_t* bflags) {
+    if (L.T < 0) return;
+    Bkt* p = minb + (L.T / 1000) % 60;
+    if (L.T > L.H) {
+        if (check && p->ws >= L.T) atomicOr(bflags, BF_LITE_STALE);
+        Bkt b;
+        bkt_reset(b, L.T, max_rt);
+        b.pass = L.pd.p; b.block = L.pd.b; b.succ = L.pd.s; b.rt = L.pd.rt; b.exc = L.pd.e;
+        if ((int64_t)L.pd.minrt < b.minrt) b.minrt = L.pd.minrt;
+        *p = b;
+        L.H = L.T;
+    } else {
+        *p = md_apply(*p, L.T, L.pd, max_rt);
     }
 }
-// the event opens second T: the pending second goes in flight, the previous flight lands
-__device__ __forceinline__ void lm_roll(LiteMin& L, Node& N, Bkt* minb, int64_t T, int32_t max_rt, uint32_t pflags) {
-    lm_finish(L, minb, max_rt);
-    if (L.T >= 0) {
-        L.fb = minb[(L.T / 1000) % 60];  // consumed at the next second change
-        L.fT = L.T;
-        L.fd = L.pd;
-        L.fly = true;
-    }
+// the event opens second T: the pending second is written
+__device__ __forceinline__ void lm_roll(LiteMin& L, Node& N, Bkt* minb, int64_t T, int32_t max_rt, uint32_t pflags,
+                                        bool check, uint32_t* bflags) {
+    lm_put(L, minb, max_rt, check, bflags);
     L.T = T;
     md_zero(L.pd);
-    // StatisticNode.totalException running sum (exc_advance): the seconds it reads are a minute old --
-    // never the one in flight -- except on a first full sum, which must see it
-    if ((pflags & PF_EXC_COUNT) && N.exc_sum_sec < T) {
-        if (N.exc_sum_sec < 0) lm_finish(L, minb, max_rt);
-        exc_advance(N, minb, T);
-    }
+    // StatisticNode.totalException running sum (exc_advance): the seconds it reads are a minute old, and slot(T)
+    // still holds the second that falls out now (it is written when the lane leaves T)
+    if ((pflags & PF_EXC_COUNT) && N.exc_sum_sec < T) exc_advance(N, minb, T);
+}
+// The ENTRY words of a chunk stay in registers (w[], newest last, bit m of mask: w[m] is an ENTRY's) and leave at the
+// top of the next chunk, before its prefetch loads issue: the loop's waits for those loads then cover stores a chunk
+// old, not ones issued moments before.  n events were shifted in; base is the first one's position.
+template <uint32_t CH>
+__device__ __forceinline__ void lite_flush(uint32_t* __restrict__ dec, uint32_t base, uint32_t n, const uint32_t (&w)[CH],
+                                           uint32_t& mask) {
+#pragma unroll
+    for (uint32_t m = 0; m < CH; ++m)
+        if ((mask >> m) & 1u) dec[base + m - (CH - n)] = w[m];
+    mask = 0;
 }
 
 // PL (XF_PLITE programs, the launch's other lanes return): ParamFlowSlot's one QPS DefaultController rule on args[0]
@@ -1383,7 +1397,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
     if (i >= m) return;
     const Seg sg = segs[order[i]];
     const uint32_t res = sg.res;
+    // Setup loads by what they depend on, each group issued together: the segment gives the program, the node (its
+    // second window and info) and the first record chunk; the program gives the rule constants and breaker states,
+    // read with clamped indices so that no `k < nf` branch puts a wait between them.
     const Prog pg = S.prog[res];
+    Node N;
+    node_load(N, S, res);
+#ifndef LITE_CH
+#define LITE_CH 4
+#endif
+    constexpr uint32_t CH = LITE_CH;
+    const uint4* r4 = reinterpret_cast<const uint4*>(recs + sg.start);
+    const uint32_t qmax = sg.len ? sg.len - 1 : 0;
+    uint4 cur[CH], nxt[CH];
+#pragma unroll
+    for (uint32_t k = 0; k < CH; ++k) cur[k] = r4[k < qmax ? k : qmax];
     if (((pg.xf & XF_PLITE) != 0) != PL) return;
     const int nf = pg.n_flow, nd = pg.n_degrade;  // <= 2 each (PF_J16)
     const DRule* rules = S.rules + pg.rule_off + (PL ? 1 : 0);  // (flow stages, then breakers)
@@ -1407,17 +1435,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
     DegParam dr[2];       // only the fields the checks read: the whole DRule would cost 28 VGPRs each
     uint32_t dslot[2] = {0, 0};
     RState ds[2];
+    if (nf + nd) {  // (a program without rules has no rule_off to read at)
+        const int last = nf + nd - 1;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (k < nf) {
-            fcnt[k] = rules[k].count;
-            fthr[k] = rules[k].grade == SG_FLOW_GRADE_THREAD;
-            fslot[k] = rules[k].slot;
-        }
-        if (k < nd) {
-            dr[k] = deg_param(rules[nf + k]);
-            dslot[k] = rules[nf + k].slot;
-            ds[k] = S.rstate[pg.rule_off + (PL ? 1 : 0) + nf + k];
+        for (int k = 0; k < 2; ++k) {  // stage k < nf / breaker k < nd, else some rule of the program: read, never used
+            const int fi = k < last ? k : last, di = nf + k < last ? nf + k : last;
+            fcnt[k] = rules[fi].count;
+            fthr[k] = rules[fi].grade == SG_FLOW_GRADE_THREAD;
+            fslot[k] = rules[fi].slot;
+            dr[k] = deg_param(rules[di]);
+            dslot[k] = rules[di].slot;
+            ds[k] = S.rstate[pg.rule_off + (PL ? 1 : 0) + di];
         }
     }
 #ifdef SG_KPROF
@@ -1432,31 +1460,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
 #else
 #define LPROF(acc)
 #endif
-    Node N;
-    node_load(N, S, res);
     const Ctx C{S.minb + (uint64_t)res * 60, cfg.max_rt, pg.pflags};
     LiteMin L;
     L.T = -1;
-    L.fly = false;
     md_zero(L.pd);
+    {
+        const int64_t sw = N.sb[0].ws > N.sb[1].ws ? N.sb[0].ws : N.sb[1].ws;
+        const int64_t sh = sw < 0 ? -1 : sw - sw % 1000;
+        L.H = sh > cfg.snap_hi ? sh : cfg.snap_hi;
+    }
+    const bool lchk = (cfg.dbg_flags & LITE_CHECK) != 0;
     const bool has_chain = (N.flags & NI_CHAIN) != 0;
     const bool chain = has_chain && cfg.switch_on;
     if (sg.len && (t0 + recs[sg.start].dt) < (N.sb[0].ws > N.sb[1].ws ? N.sb[0].ws : N.sb[1].ws))
         atomicOr(bflags, BF_BACKWARD);  // Q3: the clock went back across batches
     uint64_t pm0 = 0, pm1 = 0, pm2 = 0, pm3 = 0;  // passed bits of positions 0..255
-    // records in chunks of 4 with the next chunk in flight: one memory round trip per 4 events (the
-    // loads are unconditional with a clamped index, so the compiler's vmcnt waits cannot serialise them)
-#ifndef LITE_CH
-#define LITE_CH 4
+    // records in chunks of 4 with the next chunk in flight (the first was loaded with the setup): one memory round
+    // trip per 4 events (the loads are unconditional with a clamped index, so the compiler's vmcnt waits cannot
+    // serialise them)
+#ifndef LITE_HOLD
+#define LITE_HOLD 1  // 0: every ENTRY word is stored as it is decided (A/B)
 #endif
-    constexpr uint32_t CH = LITE_CH;
-    const uint4* r4 = reinterpret_cast<const uint4*>(recs + sg.start);
-    const uint32_t qmax = sg.len ? sg.len - 1 : 0;
-    uint4 cur[CH], nxt[CH];
+    uint32_t dw[CH], dmask = 0;  // the chunk's ENTRY words (lite_flush)
 #pragma unroll
-    for (uint32_t k = 0; k < CH; ++k) cur[k] = r4[k < qmax ? k : qmax];
+    for (uint32_t k = 0; k < CH; ++k) dw[k] = 0;
     LPROF(kta)
     for (uint32_t j0 = 0; j0 < sg.len; j0 += CH) {
+    if (j0) lite_flush<CH>(dec, sg.start + j0 - CH, CH, dw, dmask);
 #pragma unroll
     for (uint32_t k = 0; k < CH; ++k) nxt[k] = r4[j0 + CH + k < qmax ? j0 + CH + k : qmax];
 #pragma unroll 1
@@ -1477,7 +1507,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
         if (kind == SG_EV_ENTRY) {
             if (!chain) d = mk_dec(ST_NO_CHECK, 0, 0);
             else {
-                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
+                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags, lchk, bflags);
                 uint32_t status = ST_PASS, slot = 0;
                 uint64_t key = NO_KEY;
                 if (PL) {  // ParamFlowSlot: initHotParamMetricsFor, the rule's index bit, then its check
@@ -1541,10 +1571,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
                 else if (rel < 256) {
                     const uint64_t w = rel < 64 ? pm0 : rel < 128 ? pm1 : rel < 192 ? pm2 : pm3;
                     eff = ((w >> (rel & 63)) & 1) != 0;
-                } else eff = st_passed(dec[rx] & 0xFF);  // written by this lane
+                } else {  // written by this lane (a segment past the lane bins' 256: debug flag 2, SG_LANE_MAX)
+                    if (rel >= j0) lite_flush<CH>(dec, sg.start + j0, k, dw, dmask);
+                    eff = st_passed(dec[rx] & 0xFF);
+                }
             }
             if (eff && kind == SG_EV_EXIT) {  // StatisticSlot.exit
-                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
+                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags, lchk, bflags);
                 const int sl = sec_current(N, t, C.max_rt);
                 sec_add(N, sl, 0, 0, cntv, rtv, 0, rtv);
                 L.pd.s += cntv;
@@ -1564,7 +1597,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
                     }
                 }
             } else if (eff && cntv > 0) {  // ClusterNode.trace
-                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags);
+                if (T != L.T || md_full(L.pd)) lm_roll(L, N, C.minb, T, C.max_rt, C.pflags, lchk, bflags);
                 const int sl = sec_current(N, t, C.max_rt);
                 sec_add(N, sl, 0, 0, 0, 0, cntv, INT64_MAX);
                 L.pd.e += cntv;
@@ -1572,17 +1605,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PL ? LITE_P
             }
             LPROF(ktc)
         }
-        if (kind == SG_EV_ENTRY) dec[sg.start + j] = d;  // k_post reads ENTRY words only
+        // k_post reads ENTRY words only
+#if LITE_HOLD
+#pragma unroll
+        for (uint32_t m = 0; m + 1 < CH; ++m) dw[m] = dw[m + 1];
+        dw[CH - 1] = d;
+        dmask = (dmask >> 1) | (kind == SG_EV_ENTRY ? 1u << (CH - 1) : 0u);
+#else
+        if (kind == SG_EV_ENTRY) dec[sg.start + j] = d;
+#endif
     }
 #pragma unroll
     for (uint32_t k = 0; k < CH; ++k) cur[k] = nxt[k];
     }
-    // the last two seconds' minute buckets
-    lm_finish(L, C.minb, C.max_rt);
-    if (L.T >= 0) {
-        Bkt* b = C.minb + (L.T / 1000) % 60;
-        *b = md_apply(*b, L.T, L.pd, C.max_rt);
+    if (sg.len) {
+        const uint32_t jl = (sg.len - 1) / CH * CH;
+        lite_flush<CH>(dec, sg.start + jl, sg.len - jl, dw, dmask);
     }
+    lm_put(L, C.minb, C.max_rt, lchk, bflags);  // the last second's minute bucket
     node_store(N, S, res, pg.pflags);
 #pragma unroll
     for (int k = 0; k < 2; ++k)

@@ -233,12 +233,15 @@ enum : uint8_t { ST_PASS = 0, ST_PASS_WAIT = 1, ST_BLOCK_FLOW = 2, ST_BLOCK_DEGR
 
 #define HEAD_OFF 16384u  // DevCfg.dbg_flags: the cooperative owner decides XF_HEADT / XF_HEADR heads too (A/B)
 #define TABLES_ALL 32768u  // SG_DEBUG_FLAGS: the hot / cold group stage builds the side tables for every position (A/B)
+#define LITE_CHECK 65536u  // DevCfg.dbg_flags (SG_LITE_CHECK=1): k_lite reads the window start of every minute bucket it
+                           // stores without a load and raises BF_LITE_STALE if the bucket was not stale
 struct DevCfg {
     int32_t max_rt;
     int32_t occupy_timeout;
     int32_t max_chain;
     int32_t switch_on;
-    uint64_t reserved0;
+    int64_t snap_hi;     // highest second a metrics snapshot created / reset minute buckets at (-1: none): k_snap_count
+                         // writes the bucket of its `now` without moving the second window (k_lite's stale rule)
     uint64_t ring_mask;
     uint32_t dbg_flags;  // SG_DEBUG_FLAGS experiment switches (0 in production)
     uint32_t heads;      // some program is XF_HEADT / XF_HEADR: the head owner (head.hip) runs beside the bins
@@ -470,7 +473,9 @@ enum : uint32_t { BF_PRIORITIZED = 1,
                   BF_MULTI_LINK = 128,  // an ENTRY is referenced by two EXITs (or two TRACEs) of the batch
                   BF_ZERO_CNT = 256,    // an ENTRY acquires 0 (it may pass inside a saturated stretch)
                   BF_TINY_FALLBACK = 4096,  // k_tiny: the batch needs the batched path (nothing decided)
-                  BF_TINY_REJECTED = 8192 };  // k_tiny: the batch's checks failed before any decision
+                  BF_TINY_REJECTED = 8192,
+                  BF_LITE_STALE = 16384 };  // k_lite under LITE_CHECK: a minute bucket stored without a load held its second or
+                                            // a later one (internal error)  // k_tiny: the batch's checks failed before any decision
 
 // One event in resource-sorted order (16 B), built by k_prep from the caller's 24-byte
 // sg_event so that every decide kernel streams its segment with coalesced loads.

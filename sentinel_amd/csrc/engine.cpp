@@ -556,6 +556,7 @@ struct sg_engine {
     // device state
     Bkt* d_sec = nullptr;
     Bkt* d_minb = nullptr;
+    int64_t snap_hi = -1;  // highest second of a metrics snapshot's `now` (DevCfg.snap_hi)
     NodeInfo* d_info = nullptr;
     Prog* d_prog = nullptr;
     DRule* d_rules = nullptr;
@@ -867,6 +868,8 @@ static int collect(sg_engine* e, int k) {
     if (bflags & BF_BACKWARD)
         return fail(SG_EINVAL, "event timestamps must be non-decreasing across batches (SURVEY Q3)");
     if (bflags & BF_AUX_FULL) return fail(SG_ECAPACITY, "origin/context node pool full (raise aux_node_capacity)");
+    if (bflags & BF_LITE_STALE)
+        return fail(SG_ESTATE, "internal error (SG_LITE_CHECK): k_lite stored a minute bucket without a load that was not stale");
     // A map that could not place a key has already committed its ring bit and live count (a ghost entry), and a
     // failed k_pq invariant leaves its maps in an unknown state: the engine refuses every later batch.
     if (bflags & BF_PQ_INVARIANT)
@@ -1363,6 +1366,7 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (const char* v = std::getenv("SG_J4_MAX")) { e->j4_max = (uint32_t)std::strtoul(v, nullptr, 0); e->bins_pinned = true; }
     if (const char* v = std::getenv("SG_PIPELINE")) e->pipeline = v[0] == '1';
     if (const char* v = std::getenv("SG_TINY")) e->tiny_on = v[0] != '0';
+    if (const char* v = std::getenv("SG_LITE_CHECK")) { if (v[0] == '1') e->dbg_flags |= LITE_CHECK; }
     if (const char* v = std::getenv("SG_RADIX_BELOW")) e->radix_below = std::strtoull(v, nullptr, 0);
     if (const char* v = std::getenv("SG_TOK_WIDE")) e->tok_wide = std::atoi(v) == 512 ? 512u : 1024u;
     if (const char* v = std::getenv("SG_TOK_LIGHT")) e->tok_light = (uint32_t)std::strtoul(v, nullptr, 0);
@@ -2584,6 +2588,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     dc.max_chain = e->cfg.max_slot_chain_size;
     dc.switch_on = e->cfg.switch_on;
     dc.ring_mask = ring_mask;
+    dc.snap_hi = e->snap_hi;
     dc.dbg_flags = e->dbg_flags;
     dc.heads = e->has_head ? 1u : 0u;
     DevState S{};
@@ -2910,6 +2915,7 @@ static int tiny_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext, 
     dc.max_chain = e->cfg.max_slot_chain_size;
     dc.switch_on = e->cfg.switch_on;
     dc.ring_mask = (1ull << e->cfg.status_ring_log2) - 1;
+    dc.snap_hi = e->snap_hi;
     dc.dbg_flags = e->dbg_flags;
     dc.heads = e->has_head ? 1u : 0u;
     DevState S{};
@@ -3147,6 +3153,7 @@ int sg_snapshot_metrics(sg_engine* e, int64_t now_ms, sg_metric_node* out, uint6
         e->snap_cap = cap;
     }
     if (!e->d_part) { int rc = ensure_batch(e, 1); if (rc) return rc; }
+    e->snap_hi = std::max(e->snap_hi, now_ms - now_ms % 1000);  // k_snap_count writes the bucket of now (DevCfg.snap_hi)
     HIPCHK(launch_snapshot(e->d_minb, e->d_info, R, now_ms, e->cfg.statistic_max_rt, e->d_snap_cnt, e->d_snap_off,
                            e->d_part, e->d_small + 3, dev_out ? out : e->d_snap_out, dev_out || out ? cap : 0,
                            e->stream));
