@@ -171,7 +171,8 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
                                                  uint32_t* __restrict__ mixlen, uint32_t mix_wide, uint32_t head_min,
                                                  const uint16_t* __restrict__ hot_tab, uint32_t nhot,
                                                  const uint32_t* __restrict__ nhotseg, uint32_t* __restrict__ need_hot,
-                                                 uint32_t* __restrict__ need_blk) {
+                                                 uint32_t* __restrict__ need_blk, const uint32_t* __restrict__ bmax,
+                                                 uint32_t skip_min, uint32_t* __restrict__ nmark) {
     __shared__ uint32_t cnt[N_BINS];
     for (uint32_t b = threadIdx.x; b < N_BINS; b += blockDim.x) cnt[b] = 0;
     __syncthreads();
@@ -233,18 +234,26 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
             if (sg.len <= AUX_SHORT) aux_short = true;
             else aux_np = (sg.len + AUX_PIECE - 1) / AUX_PIECE;
         }
-        const uint32_t rank = atomicAdd(&cnt[bin], 1u);
-        sg.bin = bin | (auxp ? SEG_AUXP : 0u) | (rank << 8);
-        segs[s] = sg;
         // Side tables (forward links, bst[]) are read by the owners that skip frozen stretches only: k_grp_records and
-        // k_block_sums, which run after this kernel, build them for the segments marked here.  A hot segment
-        // (segs[0 .. *nhotseg)) marks its hot id, a cold one the 1024-position blocks it touches (whole words of 32
-        // blocks where it spans them); a marked block gets the tables of all its positions, its neighbours' included.
+        // k_block_sums, which run after this kernel, build them for the segments marked here.  An owner of NW waves
+        // skips a stretch of more than skip_min * NW / 16 positions, and a stretch lies inside one 500 ms bucket, so a
+        // hot segment (segs[0 .. *nhotseg)) marks its hot id only if some bucket can hold that many of its events
+        // (bmax: k_hot_bmax's upper bound), a cold one the 1024-position blocks it touches (whole words of 32 blocks
+        // where it spans them) only if it is that long at all; a marked block gets the tables of all its positions,
+        // its neighbours' included.  SEG_TABS tells the owner (k_jac's skip_on) that its tables exist: exactness
+        // does not depend on the bound, only the traffic does.  need_blk == null: the tables everywhere.
+        bool tabs = !need_blk;
         if (need_blk && (bin == BIN_J4 || bin == BIN_J8 || bin == BIN_J16) && sg.len) {
+            const uint32_t nw = bin == BIN_J4 ? 4u : bin == BIN_J8 ? 8u : 16u;
+            const uint32_t thr = skip_min * nw / 16 > 0 ? skip_min * nw / 16 : 1u;  // (k_jac's skip_min)
             if (s < *nhotseg) {
                 const uint32_t hid = hot_tab[sg.res];
-                if (hid < nhot) need_hot[hid] = 1u;
-            } else {
+                if (hid < nhot && bmax[hid] > thr) {
+                    need_hot[hid] = 1u;
+                    atomicAdd(nmark, 1u);  // (diagnostics: sgx_hot_marked)
+                    tabs = true;
+                }
+            } else if (sg.len > thr) {
                 const uint32_t b0 = sg.start >> 10, b1 = (sg.start + sg.len - 1) >> 10;
                 for (uint32_t wd = b0 >> 5; wd <= (b1 >> 5); ++wd) {
                     uint32_t m32 = 0xFFFFFFFFu;
@@ -252,8 +261,12 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
                     if (wd == (b1 >> 5)) m32 &= 0xFFFFFFFFu >> (31 - (b1 & 31));
                     atomicOr(&need_blk[wd], m32);
                 }
+                tabs = true;
             }
         }
+        const uint32_t rank = atomicAdd(&cnt[bin], 1u);
+        sg.bin = bin | (auxp ? SEG_AUXP : 0u) | (tabs ? SEG_TABS : 0u) | (rank << SEG_RANK_SHIFT);
+        segs[s] = sg;
     }
     if (aux) {  // (wave-uniform: every lane of the wave takes part)
         const uint32_t o = wave_alloc(aux + 0, aux_short ? 1u : 0u);
@@ -279,9 +292,9 @@ __global__ __launch_bounds__(256) void k_seg_order(Seg* __restrict__ segs, const
                                                    uint32_t* __restrict__ order) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= *mp) return;
-    const uint32_t v = segs[s].bin, bin = v & 0x7F;
-    order[off[(uint64_t)bin * nblk + blockIdx.x] + (v >> 8)] = s;
-    segs[s].bin = v & 0xFF;  // the bin | SEG_AUXP
+    const uint32_t v = segs[s].bin, bin = v & 0x3F;
+    order[off[(uint64_t)bin * nblk + blockIdx.x] + (v >> SEG_RANK_SHIFT)] = s;
+    segs[s].bin = v & ((1u << SEG_RANK_SHIFT) - 1);  // the bin | SEG_AUXP | SEG_TABS
 }
 // per-bin first offsets (+ total) for the host: out[b] = off[b][0], out[N_BINS] = m
 __global__ void k_bin_offsets(const uint32_t* __restrict__ off, uint32_t nblk, const uint32_t* __restrict__ mp,
@@ -2084,7 +2097,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
     SEv nxt[EP];                    // the next tile, in flight
     JEv ev[EP];
     uint32_t gg[EP];  // outcome guesses: index of the blocking stage, nr = pass
-    const bool skip_on = SKIP && S.skip_ok && (pg.pflags & PF_FROZEN);
+    const bool skip_on = SKIP && S.skip_ok && (pg.pflags & PF_FROZEN) && (sg.bin & SEG_TABS);  // (no tables: stream)
     // positions of skipped spans: blocked ENTRYs whose dec[] words k_fill writes after this kernel
     auto in_span = [&](uint32_t rel) -> bool {
         if (!SKIP) return false;
@@ -4125,12 +4138,13 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
-                          const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, hipStream_t st) {
+                          const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
+                          uint32_t skip_min, uint32_t* nmark, hipStream_t st) {
     const uint32_t nblk = (mb + 255) / 256;
     if (!nblk) return hipSuccess;
     hipLaunchKernelGGL(k_seg_bin, dim3(nblk), dim3(256), 0, st, segs, mp, n, prog, prio, lane_max, j1_max, j4_max, force_lane,
                        blkcnt, nblk, pq_ok, pq_wide, aux, ashort, along, amulti, mixc, mix, mix_cap, mixlen, mix_wide,
-                       head_min, hot_tab, nhot, nhotseg, need_hot, need_blk);
+                       head_min, hot_tab, nhot, nhotseg, need_hot, need_blk, bmax, skip_min, nmark);
     return hipGetLastError();
 }
 // off = exclusive scan of blkcnt (bin-major); writes the per-bin offsets to bin_off[0..N_BINS]

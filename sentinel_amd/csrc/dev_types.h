@@ -257,6 +257,10 @@ struct Seg {
 #define SEG_AUXP 0x80u  // Seg.bin: the segment's origin / context nodes are updated by the aux.hip post-pass
 #define SEG_PV 0x40u    // Seg.bin: pvalue.hip decided the segment's param checks (k_pq's pre pass leaves it)
 #define SEG_PVT 0x100u  // Seg.bin: pvalue.hip's post pass updated the thread-count map (k_pq's post pass leaves it)
+#define SEG_TABS 0x200u  // Seg.bin: the segment's side tables (forward links, bst[]) exist: its owner may skip frozen
+                         // stretches (k_seg_bin; bits 0..5 the bin, 6..9 these flags, the rank inside its block above
+                         // them until k_seg_order places the segment)
+#define SEG_RANK_SHIFT 10
 
 // pvalue.hip: the value-parallel pre pass of long XF_MIX segments
 // per listed segment (the wide XF_MIX list): what the pre pass found

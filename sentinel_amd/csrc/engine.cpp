@@ -51,6 +51,8 @@ hipError_t launch_grp_first(const sg_event* ev, uint64_t n, uint32_t max_res, ui
                             hipStream_t st);
 hipError_t launch_hot_scan(uint32_t* C, uint32_t nblocks, uint32_t nhot, uint32_t* part, uint32_t* hb, uint32_t* total,
                            hipStream_t st);
+hipError_t launch_hot_bmax(const sg_event* ev, uint32_t nblocks, const uint32_t* P, uint32_t nhot, const uint32_t* hb,
+                           uint32_t* edges, uint32_t* bmax, hipStream_t st);
 hipError_t launch_grp_records(const sg_event* ev, uint64_t n, uint64_t gbase, uint64_t ring_mask, int32_t max_rt,
                               const uint32_t* words, const uint32_t* P, uint32_t nhot, uint32_t nblocks,
                               const uint32_t* hb, SEv* recs, uint32_t* svals, uint32_t* prev,
@@ -89,7 +91,8 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
-                          const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, hipStream_t st);
+                          const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
+                          uint32_t skip_min, uint32_t* nmark, hipStream_t st);
 // aux.hip
 hipError_t launch_aux(const SEv* recs, const Seg* segs, const uint32_t* aux, const uint32_t* ashort,
                       const uint64_t* along, uint64_t* apiece, const uint64_t* amulti, const DevState& S, const DevCfg& cfg,
@@ -584,6 +587,7 @@ struct sg_engine {
         uint32_t* d_ccnt = nullptr;    // hot / cold group stage: per-tile cold counts, the cold segments' tile scratch
         bool radix = false;            // this batch took the radix group stage (d_posof), else the hot / cold one
         uint32_t nhot = 0;             // ... with these hot ids (its words and P in d_flag / d_pos)
+        uint32_t hot_marked = 0;       // ... of which k_seg_bin marked this many for the side tables (d_bsmall[73])
         Seg* d_segs = nullptr;
         uint64_t* d_cand = nullptr;
         uint32_t* d_bsmall = nullptr;  // [0] bflags [1] nseg [2] ncand [3] nprev [4..5] t0 [8..8+N_BINS] bin offsets
@@ -617,9 +621,12 @@ struct sg_engine {
     uint32_t* d_hot_part = nullptr;  // the hot scan's per-chunk partials ((max tiles / 64 + 2) x HOT_MAX words)
     uint32_t* d_hot_hb = nullptr;    // per hot id: first sorted position, total (2 x HOT_MAX words)
     // which side tables (forward links, bst[]) the batch being grouped needs (k_seg_bin): one word per hot id, then
-    // one bit per 1024-position block of the cold region
+    // one bit per 1024-position block of the cold region, then per hot id the most events one 500 ms bucket can hold
+    // (k_hot_bmax; d_edges: its bucket-opening tiles, count first)
     uint32_t* d_need = nullptr;
     uint64_t need_words = 0;
+    uint32_t* d_edges = nullptr;
+    uint32_t hot_marked_last = 0;  // hot ids marked for the side tables in the last collected batch (sgx_hot_marked)
     bool radix_group = false;    // SG_DEBUG_FLAGS & 8192: the all-radix group stage (A/B)
     uint64_t radix_below = 1u << 18;  // SG_RADIX_BELOW: batches of fewer events take the radix group stage (the drop-in's
                                       // 65,536-event batches: 36 vs 30-32 M entries/s on the hot / cold one)
@@ -819,8 +826,10 @@ int ensure_batch(sg_engine* e, uint64_t n) {
     dfree(e->d_hot_part);
     dfree(e->d_hot_hb);
     dfree(e->d_need);
-    e->need_words = hot_max() + c / 32768 + 2;
+    dfree(e->d_edges);
+    e->need_words = hot_max() + c / 32768 + 2 + hot_max();
     HIPCHK(hipMalloc(&e->d_need, e->need_words * 4));
+    HIPCHK(hipMalloc(&e->d_edges, (nblocks + 2) * 4));
     HIPCHK(hipMalloc(&e->d_hot_part, (nblocks / 16 + 2) * hot_max() * 4));  // (HS_TC >= 16 tiles a chunk)
     HIPCHK(hipMalloc(&e->d_hot_hb, 2 * hot_max() * 4));
     for (auto& B : e->slot) {
@@ -860,6 +869,7 @@ static int collect(sg_engine* e, int k) {
     HIPCHK(hipMemcpyAsync(&nspan, B.d_bsmall + 120, 4, hipMemcpyDeviceToHost, e->gstream));
     HIPCHK(hipStreamSynchronize(e->gstream));
     e->spans_total += nspan;
+    e->hot_marked_last = B.hot_marked;
     // Flags the decide kernels raise (the group stage's own checks return before the decide stage runs):
     // an EXIT/TRACE whose reference names an event that is not an earlier ENTRY of its resource, and a
     // batch starting before the last window a resource already holds (the clock went back).
@@ -1412,6 +1422,13 @@ extern "C" unsigned long long sgx_spans_total(sg_engine* e) {
     (void)drain(e);
     return e->spans_total;
 }
+// diagnostics export: hot ids whose side tables the last collected batch built (0 on the radix stage and with
+// SG_DEBUG_FLAGS & 32768, which build them everywhere)
+extern "C" unsigned int sgx_hot_marked(sg_engine* e) {
+    if (!e) return 0;
+    (void)drain(e);
+    return e->hot_marked_last;
+}
 // diagnostics export: zero the SG_DEBUG counters ([20] is a running minimum)
 extern "C" int sgx_debug_reset(sg_engine* e) {
     if (!e || !e->d_dbg) return 0;
@@ -1513,7 +1530,7 @@ int sg_engine_destroy(sg_engine* e) {
     if (e->gstream) (void)hipStreamSynchronize(e->gstream);
     for (auto& B : e->slot) free_slot(B);
     dfree(e->d_auth); dfree(e->d_auth_ids);
-    dfree(e->d_prio); dfree(e->d_hot_tab); dfree(e->d_hot_list); dfree(e->d_hot_part); dfree(e->d_hot_hb); dfree(e->d_need); dfree(e->d_comp); dfree(e->d_auxtab); dfree(e->d_auxpool); dfree(e->d_auxcnt); dfree(e->d_auxmeta);
+    dfree(e->d_prio); dfree(e->d_hot_tab); dfree(e->d_hot_list); dfree(e->d_hot_part); dfree(e->d_hot_hb); dfree(e->d_need); dfree(e->d_edges); dfree(e->d_comp); dfree(e->d_auxtab); dfree(e->d_auxpool); dfree(e->d_auxcnt); dfree(e->d_auxmeta);
     dfree(e->d_pflow); dfree(e->d_phot); dfree(e->d_pftab); dfree(e->d_pvtab); dfree(e->d_preq); dfree(e->d_pvals);
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_nslimit); dfree(e->d_nsb); dfree(e->d_borrow); dfree(e->d_keyring);
     dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx); dfree(e->d_tbounds);
@@ -2463,10 +2480,14 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     // 1,024-lane one reaches its 66.5M only in a batch twice the default max_batch_events.)
     j1_max = std::min<uint32_t>(j1_max, 64u * 65000u);
     j4_max = std::min<uint32_t>(j4_max, 256u * 65000u);
+    // a shard-sized batch (see the bins above) is bound by its longest owners, whose frozen stretches are
+    // cheaper skipped than streamed from 8192 positions on (8-way C4 shards: slowest rank 1.79 -> 1.69 ms)
+    const uint32_t skip_min = (!e->skip_pinned && n < SHARD_BATCH) ? std::min<uint32_t>(e->skip_min, 8192) : e->skip_min;
     // need_hot / need_blk (the hot / cold stage; null: the side tables everywhere): the segments whose owner can skip
     // frozen stretches mark their hot id / their cold blocks, and the record kernels, which run after the bins there,
-    // build forward links and bst[] for those only
-    auto bins = [&](uint32_t* need_hot, uint32_t* need_blk) -> int {
+    // build forward links and bst[] for those only.  bmax: per hot id the most events one 500 ms bucket can hold
+    // (launch_hot_bmax): an id is marked only where that exceeds its owner's skip threshold.
+    auto bins = [&](uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax) -> int {
         if (ext) {  // the aux.hip post-pass lists of this slot
             if (int arc = ensure_aux(e, B, n)) return arc;
         }
@@ -2478,7 +2499,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
                               B.d_ashort, B.d_along, B.d_amulti, e->d_bsmall + 6, e->has_mix ? B.d_mix : nullptr,
                               (uint32_t)B.mix_cap, e->d_bsmall + 72, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
                               (e->dbg_flags & HEAD_OFF) ? 0u : e->head_min, e->d_hot_tab, e->nhot, e->d_bsmall + 80, need_hot,
-                              need_blk, gs));
+                              need_blk, bmax, skip_min, e->d_bsmall + 73, gs));
         HIPCHK(launch_scan(e->d_blkcnt, e->d_blkcnt, (uint64_t)nblk * N_BINS, e->d_part, nullptr, gs));
         HIPCHK(launch_seg_order(e->d_segs, e->d_bsmall + 1, mb, e->d_blkcnt, e->d_order, e->d_bsmall + 8, gs));
         return SG_OK;
@@ -2498,7 +2519,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         HIPCHK(launch_seg(kin, n, e->d_flag, e->d_pos, e->d_segs, gs, launch_scan, e->d_part, e->d_bsmall + 1));
         HIPCHK(launch_gather(e->d_rec_o, vin, kin, n, e->d_posof, e->d_recs, e->d_prev, e->d_bsmall + 3, e->d_link,
                              e->d_bst, e->epoch, e->d_bsmall + 0, gs));
-        if (int brc = bins(nullptr, nullptr)) return brc;
+        if (int brc = bins(nullptr, nullptr, nullptr)) return brc;
     } else {
         // ---- hot / cold group stage (kernels.hip k_grp_*): [77] hot_total (the cold region's start), [78] cold
         // events, [80] hot segments, [81] (hot_total again), [82] cold segments, [76] the next batch's hot ids
@@ -2506,7 +2527,8 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         B.nhot = nhot;
         uint32_t* words = e->d_flag;    // per event: W_HOT | W_ENT? | hot id << 12 | rank in its tile's run of the id;
                                         // cold: W_ENT? | sorted position (the last cold pass)
-        uint32_t* hot_off = e->d_pos;   // [hot id][tile] counts, scanned in place: the runs' sorted positions
+        uint32_t* hot_off = e->d_pos;   // [tile][hot id] counts (tile-major, rows of nhot words), scanned in place: the
+                                        // runs' sorted positions P (k_grp_records, k_post_w, k_hot_bmax read rows of it)
         uint32_t* ccnt = B.d_ccnt;      // per tile: cold events (compacted at the tile's start in k1 / v1)
         HIPCHK(launch_grp_first(dev_ev, n, R, e->gbase, ring_mask, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
                                 e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e),
@@ -2537,13 +2559,15 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         HIPCHK(hipMemsetAsync(e->d_bst, 0, ((n + 1023) / 1024) * 4, gs));
         // the bins first: they read only the segments, the programs and the marks of k_grp_first, and say which
         // side tables the record kernels must build (SG_DEBUG_FLAGS & 32768: all of them, as the radix stage does)
-        uint32_t *need_hot = nullptr, *need_blk = nullptr;
+        uint32_t *need_hot = nullptr, *need_blk = nullptr, *bmax = nullptr;
         if (!(e->dbg_flags & TABLES_ALL)) {
             need_hot = e->d_need;
             need_blk = e->d_need + hot_max();
+            bmax = e->d_need + e->need_words - hot_max();
             HIPCHK(hipMemsetAsync(e->d_need, 0, e->need_words * 4, gs));
+            HIPCHK(launch_hot_bmax(dev_ev, nblocks, hot_off, nhot, e->d_hot_hb, e->d_edges, bmax, gs));
         }
-        if (int brc = bins(need_hot, need_blk)) return brc;
+        if (int brc = bins(need_hot, need_blk, bmax)) return brc;
         HIPCHK(launch_grp_records(dev_ev, n, e->gbase, ring_mask, e->cfg.statistic_max_rt, words, hot_off, nhot, nblocks,
                                   e->d_hot_hb, e->d_recs, vin, e->d_prev, e->d_bsmall + 3, e->d_bst,
                                   e->d_bsmall + 0, dev_ext, dev_args, SG_MAX_CONTEXTS, e->d_link, e->epoch, need_hot,
@@ -2558,13 +2582,14 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         HIPCHK(launch_hot_build(e->d_segs, e->d_bsmall + 1, mb, hot_min, R, e->d_hot_tab, e->d_hot_list, e->nhot,
                                 e->d_bsmall + 76, gs));
     // [0] bflags [1] nseg [3] nprev [4..5] t0 [6..7] XF_MIX lists [8..8+N_BINS] bin offsets [72] wide XF_MIX events
-    // [76] the next batch's hot ids
+    // [73] hot ids marked for the side tables [76] the next batch's hot ids
     uint32_t head[77];
     static_assert(8 + N_BINS + 1 <= 72, "head layout");
     HIPCHK(hipMemcpyAsync(head, e->d_bsmall, sizeof(head), hipMemcpyDeviceToHost, gs));
     HIPCHK(hipEventRecord(B.ev[1], gs));
     HIPCHK(hipStreamSynchronize(gs));
     if (!B.radix) e->nhot = std::min<uint32_t>(head[76], hot_max());
+    B.hot_marked = head[73];
     const uint32_t m = head[1];
     const uint32_t nprev = head[3];
     int64_t t0 = 0;
@@ -2620,9 +2645,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     S.span_cap = e->span_cap;
     S.epoch = e->epoch;
     S.skip_ok = !(bflags & (BF_MULTI_LINK | BF_ZERO_CNT)) && !(e->dbg_flags & 4) ? 1u : 0u;
-    // a shard-sized batch (see the bins above) is bound by its longest owners, whose frozen stretches are
-    // cheaper skipped than streamed from 8192 positions on (8-way C4 shards: slowest rank 1.79 -> 1.69 ms)
-    S.skip_min = (!e->skip_pinned && n < SHARD_BATCH) ? std::min<uint32_t>(e->skip_min, 8192) : e->skip_min;
+    S.skip_min = skip_min;  // (the bins marked the side tables by it)
     S.ext = dev_ext;
     S.args = dev_args;
     S.aux_tab = e->d_auxtab;

@@ -421,6 +421,75 @@ __global__ __launch_bounds__(256) void k_hot_scan_c(uint32_t* __restrict__ C, ui
     }
 }
 
+// ---- bmax[h]: an upper bound of hot id h's events in any one 500 ms bucket (absolute, ts / 500, as k_jac's rounds
+// count them: a round never crosses one, so a frozen stretch an owner could skip is never longer).  Only tile
+// boundaries are looked at: with fb[t] the bucket of tile t's first event, the events of a bucket b in which some tile
+// starts lie in the tiles [t_lo, t_hi], t_lo = the tile before the first one with fb == b (it may straddle into b),
+// t_hi = the last one with fb == b (it may straddle out), and h has P[t_hi + 1][h] - P[t_lo][h] events there (its end
+// past the last tile).  A bucket in which no tile starts lies inside one tile, which some such range holds whole.
+// k_seg_bin marks a hot id for the side tables only where the bound exceeds its owner's skip threshold.
+// k_bkt_edges (one workgroup): edges[1 ..] = the tiles whose first event opens a bucket (tile 0 among them), in
+// order, edges[0] = their count.  One 8-byte load a tile (and its neighbour's), BE_ITEMS consecutive tiles a lane.
+#define BE_THREADS 1024
+#define BE_ITEMS 8
+__global__ __launch_bounds__(BE_THREADS) void k_bkt_edges(const sg_event* __restrict__ ev, uint32_t nblocks,
+                                                          uint32_t* __restrict__ edges) {
+    __shared__ uint32_t ws[BE_THREADS / 64];
+    const uint32_t t = threadIdx.x, l = t & 63, wv = t >> 6;
+    uint32_t run = 0;  // (uniform) edges so far
+    for (uint32_t c0 = 0; c0 < nblocks; c0 += BE_THREADS * BE_ITEMS) {
+        const uint32_t t0 = c0 + t * BE_ITEMS;
+        int64_t ts[BE_ITEMS + 1];  // ts[k] = the first timestamp of tile t0 + k - 1 (clamped, unconditional loads)
+#pragma unroll
+        for (int k = 0; k <= BE_ITEMS; ++k) {
+            uint32_t tl = (t0 + k) ? t0 + k - 1 : 0u;
+            if (tl >= nblocks) tl = nblocks - 1;
+            ts[k] = ev[(uint64_t)tl * RS_TILE].ts;
+        }
+        uint32_t f = 0;
+#pragma unroll
+        for (int k = 0; k < BE_ITEMS; ++k)
+            if (t0 + k < nblocks && (t0 + k == 0 || ts[k + 1] / 500 != ts[k] / 500)) f |= 1u << k;
+        const uint32_t c = (uint32_t)__popc(f);
+        uint32_t x = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if ((int)l >= o) x += y;
+        }
+        if (l == 63) ws[wv] = x;
+        __syncthreads();
+        uint32_t pre = 0, all = 0;
+        for (uint32_t k = 0; k < BE_THREADS / 64; ++k) { if (k < wv) pre += ws[k]; all += ws[k]; }
+        uint32_t o = 1 + run + pre + x - c;
+#pragma unroll
+        for (int k = 0; k < BE_ITEMS; ++k)
+            if ((f >> k) & 1u) edges[o++] = t0 + k;
+        run += all;
+        __syncthreads();  // (ws is rewritten by the next chunk)
+    }
+    if (t == 0) edges[0] = run;
+}
+// k_hot_bmax: BM_EDGES buckets a workgroup, one hot id a lane (rows of P read contiguous), the maximum by atomicMax
+// into bmax (zeroed before).  The grid covers nblocks edges, the most there can be; workgroups past the count leave.
+#define BM_EDGES 32u
+__global__ __launch_bounds__(256) void k_hot_bmax(const uint32_t* __restrict__ P, uint32_t nblocks, uint32_t nhot,
+                                                  const uint32_t* __restrict__ hb, const uint32_t* __restrict__ edges,
+                                                  uint32_t* __restrict__ bmax) {
+    const uint32_t ne = edges[0], j0 = blockIdx.y * BM_EDGES, j1 = min(ne, j0 + BM_EDGES);
+    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
+    if (j0 >= ne || h >= nhot) return;
+    const uint32_t end = hb[h] + hb[HOT_MAX + h];
+    uint32_t m = 0;
+    for (uint32_t j = j0; j < j1; ++j) {
+        const uint32_t a = edges[1 + j], b = j + 1 < ne ? edges[2 + j] : nblocks;
+        const uint32_t lo = P[(uint64_t)(a ? a - 1 : 0u) * nhot + h];
+        const uint32_t hi = b < nblocks ? P[(uint64_t)b * nhot + h] : end;
+        m = max(m, hi - lo);
+    }
+    if (m) atomicMax(&bmax[h], m);
+}
+
 // The sorted position of event j from its word (hot: the tile's run start + rank; cold: the word itself)
 __device__ __forceinline__ uint32_t grp_pos(uint64_t j, uint32_t wd, const uint32_t* __restrict__ P, uint32_t nhot) {
     if (wd & W_HOT) return P[(j / RS_TILE) * nhot + ((wd >> 12) & (HOT_MAX - 1))] + (wd & 0xFFFu);
@@ -1176,6 +1245,15 @@ hipError_t launch_hot_scan(uint32_t* C, uint32_t nblocks, uint32_t nhot, uint32_
     hipLaunchKernelGGL(k_hot_scan_a, dim3(nch), dim3(256), 0, st, C, nblocks, nhot, part);
     hipLaunchKernelGGL(k_hot_scan_b, dim3(1), dim3(HOT_MAX), 0, st, part, nch, nhot, hb, total);
     hipLaunchKernelGGL(k_hot_scan_c, dim3(nch), dim3(256), 0, st, C, nblocks, nhot, part, hb);
+    return hipGetLastError();
+}
+// after launch_hot_scan (P, hb); edges: scratch of nblocks + 2 words; bmax: nhot words, zeroed by the caller
+hipError_t launch_hot_bmax(const sg_event* ev, uint32_t nblocks, const uint32_t* P, uint32_t nhot, const uint32_t* hb,
+                           uint32_t* edges, uint32_t* bmax, hipStream_t st) {
+    if (!nhot || !nblocks) return hipSuccess;
+    hipLaunchKernelGGL(k_bkt_edges, dim3(1), dim3(BE_THREADS), 0, st, ev, nblocks, edges);
+    hipLaunchKernelGGL(k_hot_bmax, dim3((nhot + 255) / 256, (nblocks + BM_EDGES - 1) / BM_EDGES), dim3(256), 0, st, P,
+                       nblocks, nhot, hb, edges, bmax);
     return hipGetLastError();
 }
 hipError_t launch_grp_records(const sg_event* ev, uint64_t n, uint64_t gbase, uint64_t ring_mask, int32_t max_rt,

@@ -228,6 +228,15 @@ class Engine:
         fn.argtypes = [C.c_void_p]
         return int(fn(self.h))
 
+    def hot_marked(self) -> int:
+        """Hot ids whose side tables (forward links, bst[]) the last batch built: those whose owner can skip a frozen
+        stretch inside some 500 ms bucket (diagnostics export sgx_hot_marked; 0 where the tables are built
+        everywhere)."""
+        fn = lib().sgx_hot_marked
+        fn.restype = C.c_uint
+        fn.argtypes = [C.c_void_p]
+        return int(fn(self.h))
+
     def read_aux_node(self, res: int, kind: int, node_id: int):
         """An origin (kind 0, origin id) / context (kind 1, context id) node of res: second window [2, 8], thread,
         minute pass history [2, 2] ({ws, pass} per second parity); None if absent (diagnostics export
