@@ -360,6 +360,40 @@ int sg_load_authority_rules(sg_engine* e, const sg_authority_rule* rules, uint32
  * equivalent pure function) for args[0] of every entry. */
 int sg_param_key(sg_engine* e, const char* value, const char* class_type, uint64_t* out_key);
 
+/* Exact parameter keys.  sg_param_key is a pure function, and for three kinds of value its 64-bit word is a
+ * hash: Strings (and every class turned into text), longs outside +-2^59 and doubles.  Two such values can
+ * share a word and then share a token bucket, which ParamFlowChecker's equals()-compared maps never do
+ * (param/.../ParameterMetric.java:88-104).  sg_param_intern types the value the same way and gives equal keys
+ * only for equal values (String: the bytes; Long: the parsed value; Double: Double.equals -- bit equality,
+ * 0.0 != -0.0, one NaN): the engine keeps a dictionary of the hashed values in use.  A value that collides
+ * with nothing gets the word sg_param_key gives, so callers of either function interoperate; the other kinds
+ * hold their value in the key and are returned as sg_param_key returns them.  A NULL value gives key 0.
+ * sg_param_intern(_batch) may be called from any number of threads, also while batches are submitted.
+ * sg_load_param_rules interns and pins the hot items of the loaded rules (local and cluster), so two hot items
+ * whose words collide keep their own thresholds.  Keys of the intern path belong to the engine that gave them.
+ *
+ * The dictionary is bounded like the reference's LRU maps: sg_param_keys_sweep drops the entries the device no
+ * longer holds.  The epoch rule: the engine has an epoch, starting at 0, and every entry remembers the epoch of
+ * its last intern (insert or hit).  A sweep waits for every submitted batch, then sets E = epoch and
+ * epoch = E + 1.  Its candidates are the unpinned entries last interned before E.  The device marks the
+ * candidates whose key is a live key of a ParameterMetric map (rule maps and thread-count maps), a word of the
+ * ENTRY key ring, or the key of a claimed (flow, value) slot of the token server.  The unmarked candidates are
+ * dropped, unless an intern hit them while the device was scanning; a dropped value that returns is interned
+ * anew (its pure key, if that is free again).
+ * Caller contract: a key may be used in events (and token requests) submitted before the start of the second
+ * sweep that follows the intern call that returned it.  Sweep at a period far above the time a key spends
+ * between its intern and its submit (the Java binding: 60 s by default).  Call sg_param_keys_sweep from the
+ * thread that submits.
+ *
+ * sg_param_keys_stats writes up to cap values and returns how many (as sg_last_timings does): [0] entries,
+ * [1] entries whose key is not their pure key, [2] pinned entries, [3] sweeps so far, and of the last sweep
+ * [4] candidates, [5] candidates the device held, [6] entries dropped, [7] its duration in microseconds. */
+int sg_param_intern(sg_engine* e, const char* value, const char* class_type, uint64_t* out_key);
+int sg_param_intern_batch(sg_engine* e, const char* const* values, const char* const* class_types, uint32_t n,
+                          uint64_t* out_keys);
+int sg_param_keys_sweep(sg_engine* e);
+int sg_param_keys_stats(sg_engine* e, uint64_t* out, int cap);
+
 /* Decide a batch: the ProcessorSlot chain Statistic -> ParamFlow -> Flow ->
  * Degrade (param/slots/HotParamSlotChainBuilder.java:38-51) for every ENTRY,
  * StatisticSlot.exit (core/slots/statistic/StatisticSlot.java:136-173) for every

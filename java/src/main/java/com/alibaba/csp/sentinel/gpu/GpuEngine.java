@@ -13,6 +13,7 @@ import java.util.concurrent.TimeUnit;
 import java.util.concurrent.locks.LockSupport;
 
 import com.alibaba.csp.sentinel.config.SentinelConfig;
+import com.alibaba.csp.sentinel.log.RecordLog;
 import com.alibaba.csp.sentinel.node.IntervalProperty;
 import com.alibaba.csp.sentinel.node.SampleCountProperty;
 
@@ -100,6 +101,11 @@ final class GpuEngine {
     private final Arena arena = Arena.ofShared();
     private MemorySegment evBuf, extBuf, outBuf, argBuf;
     private int evCap, argCap;
+    // The key dictionary (ParamKeys) is swept on this thread between batches: a key is interned while its batch
+    // is filled and submitted before the next sweep, and the period is far above the batching latency, which is
+    // what sg_param_keys_sweep's caller contract needs.  0 or less: never.
+    private final long keySweepNanos = TimeUnit.SECONDS.toNanos(Long.getLong("sentinel.gpu.keySweepSeconds", 60L));
+    private long lastKeySweep = System.nanoTime();
 
     private GpuEngine() {
         final java.lang.foreign.StructLayout C = SentinelGpu.SG_CONFIG;
@@ -263,6 +269,7 @@ final class GpuEngine {
         while (true) {
             try {
                 Op first = queue.poll(50, TimeUnit.MILLISECONDS);
+                sweepKeysIfDue();
                 if (first == null) {
                     continue;
                 }
@@ -282,6 +289,24 @@ final class GpuEngine {
                 }
             } finally {
                 batch.clear();
+            }
+        }
+    }
+
+    /** sg_param_keys_sweep once the period has passed; a failure is the next batch's to report. */
+    private void sweepKeysIfDue() {
+        if (keySweepNanos <= 0 || poisoned || System.nanoTime() - lastKeySweep < keySweepNanos) {
+            return;
+        }
+        lastKeySweep = System.nanoTime();
+        synchronized (nativeLock) {
+            try {
+                int rc = (int)SentinelGpu.PARAM_KEYS_SWEEP.invokeExact(handle);
+                if (rc != SentinelGpu.SG_OK) {
+                    RecordLog.warn("sentinel_gpu: parameter key sweep failed (" + rc + ")");
+                }
+            } catch (Throwable t) {
+                RecordLog.warn("sentinel_gpu: parameter key sweep failed", t);
             }
         }
     }
@@ -356,7 +381,7 @@ final class GpuEngine {
             argBuf.set(JAVA_LONG, o + A_KEY, 0L);
             argBuf.set(JAVA_INT, o + A_KIND, SentinelGpu.ARG_NULL);
         } else {
-            argBuf.set(JAVA_LONG, o + A_KEY, ParamKeys.of(v));
+            argBuf.set(JAVA_LONG, o + A_KEY, ParamKeys.of(handle, v));
             argBuf.set(JAVA_INT, o + A_KIND, SentinelGpu.ARG_SCALAR);
         }
         argBuf.set(JAVA_INT, o + A_LEN, 0);

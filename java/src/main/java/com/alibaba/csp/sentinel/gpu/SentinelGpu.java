@@ -207,6 +207,13 @@ final class SentinelGpu {
     static final MethodHandle LOAD_AUTHORITY_RULES = fn("sg_load_authority_rules",
         rc(ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
     static final MethodHandle PARAM_KEY = fn("sg_param_key", rc(ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+    /** Exact parameter keys: (engine, value, classType, long* key) / (engine, char** values, char** classTypes, n,
+     *  long* keys) / (engine) / (engine, long* out, cap) -> values written. */
+    static final MethodHandle PARAM_INTERN = fn("sg_param_intern", rc(ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+    static final MethodHandle PARAM_INTERN_BATCH = fn("sg_param_intern_batch",
+        rc(ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
+    static final MethodHandle PARAM_KEYS_SWEEP = fn("sg_param_keys_sweep", rc(ADDRESS));
+    static final MethodHandle PARAM_KEYS_STATS = fn("sg_param_keys_stats", rc(ADDRESS, ADDRESS, JAVA_INT));
     static final MethodHandle SUBMIT = fn("sg_submit", rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));
     static final MethodHandle SUBMIT_ASYNC = fn("sg_submit_async", rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));
     static final MethodHandle SUBMIT_EX = fn("sg_submit_ex",

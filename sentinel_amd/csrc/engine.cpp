@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +23,7 @@
 #include "../../include/sentinel_gpu.h"
 #include "authority.h"
 #include "dev_types.h"
+#include "pkeys.h"
 #include "pmap.h"  // (pm_buckets: sg_param_thread_count)
 
 namespace sg {
@@ -191,6 +193,11 @@ hipError_t launch_tok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_
 hipError_t launch_ptok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
                             const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
                             uint32_t mask, sg_token_result* res, uint32_t* flags, hipStream_t st);
+// keysweep.hip
+hipError_t launch_keysweep(const PMap* pmap, uint32_t nm, const PBucket* pbkt, uint64_t pool_nb, const uint64_t* pbm,
+                           uint64_t bm_words, const uint64_t* key_ring, uint64_t ring_n, const PVal* pvtab,
+                           uint64_t pv_n, const uint64_t* tkey, const uint32_t* tidx, uint32_t tmask, uint32_t* marks,
+                           hipEvent_t* ev, hipStream_t st);
 } // namespace sg
 
 using namespace sg;
@@ -298,50 +305,9 @@ void hashset_order(const std::vector<int32_t>& hashes, std::vector<int>& order) 
 }
 
 // ---- param value keys (ParamFlowRuleUtil.parseItemValue typing, ParamFlowRuleUtil.java:85-121)
-constexpr uint64_t KEY_MASK = 0x0FFFFFFFFFFFFFFFULL;
-uint64_t fnv64(const char* s) {
-    uint64_t h = 1469598103934665603ULL;
-    for (; *s; ++s) { h ^= (unsigned char)*s; h *= 1099511628211ULL; }
-    return h;
-}
-uint64_t mix64(uint64_t x) {
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL;
-    x ^= x >> 27; x *= 0x94d049bb133111ebULL;
-    x ^= x >> 31; return x;
-}
-uint64_t tagged(uint64_t tag, uint64_t v) { return (tag << 60) | (v & KEY_MASK); }
-bool ieq(const char* a, const char* b) {
-    for (; *a && *b; ++a, ++b) if (std::tolower((unsigned char)*a) != std::tolower((unsigned char)*b)) return false;
-    return *a == *b;
-}
-uint64_t param_key(const char* v, const char* t) {
-    if (!v) return 0;
-    auto is = [&](const char* a, const char* b) { return t && (!std::strcmp(t, a) || !std::strcmp(t, b)); };
-    if (blank(t) || !std::strcmp(t, "java.lang.String") || !std::strcmp(t, "String")) return tagged(1, fnv64(v) & KEY_MASK);
-    if (is("int", "java.lang.Integer")) return tagged(2, (uint32_t)(int32_t)std::strtol(v, nullptr, 10));
-    if (is("long", "java.lang.Long")) {
-        long long x = std::strtoll(v, nullptr, 10);
-        if (x >= -(1LL << 59) && x < (1LL << 59)) return tagged(3, (uint64_t)x);
-        return tagged(3, (fnv64(v) & KEY_MASK) | (1ULL << 59));
-    }
-    if (is("double", "java.lang.Double")) {
-        double d = std::strtod(v, nullptr);
-        uint64_t u;
-        std::memcpy(&u, &d, 8);
-        return tagged(4, mix64(u));
-    }
-    if (is("float", "java.lang.Float")) {
-        float f = std::strtof(v, nullptr);
-        uint32_t u;
-        std::memcpy(&u, &f, 4);
-        return tagged(5, u);
-    }
-    if (is("byte", "java.lang.Byte")) return tagged(6, (uint8_t)(int8_t)std::strtol(v, nullptr, 10));
-    if (is("short", "java.lang.Short")) return tagged(7, (uint16_t)(int16_t)std::strtol(v, nullptr, 10));
-    if (is("boolean", "java.lang.Boolean")) return tagged(8, ieq(v, "true") ? 1 : 0);
-    if (!std::strcmp(t, "char")) return tagged(9, (unsigned char)v[0]);
-    return tagged(1, fnv64(v) & KEY_MASK);
-}
+uint64_t mix64(uint64_t x) { return pk::mix64(x); }
+// the pure key of a value (sg_param_key): typing and hashing are pkeys.h's, which the dictionary shares
+uint64_t param_key(const char* v, const char* t) { return pk::pure_key<pk::StdHash>(v, t); }
 
 // ----------------------------------------------------------------- rule records
 struct FlowR {
@@ -443,7 +409,8 @@ bool param_valid(const sg_param_rule& r) { // ParamFlowRuleUtil.isValidRule (Par
     }
     return true;
 }
-ParamR make_param(const sg_param_rule& s) {
+// key: the hot items' keys (the engine's dictionary: two items whose pure keys collide keep their own counts)
+ParamR make_param(const sg_param_rule& s, const std::function<uint64_t(const char*, const char*)>& key) {
     ParamR p;
     p.r = s;
     p.res = sv(s.resource);
@@ -460,7 +427,7 @@ ParamR make_param(const sg_param_rule& s) {
         p.items.push_back(q);
         // ParamFlowRuleUtil.parseHotItems (ParamFlowRuleUtil.java:62-83)
         if (!it.object || !it.has_count || it.count < 0) continue;
-        uint64_t k = param_key(it.object, it.class_type);
+        uint64_t k = key(it.object, it.class_type);
         bool found = false;
         for (auto& h : p.hot) if (h.first == k) { h.second = it.count; found = true; }
         if (!found) p.hot.push_back({k, it.count});
@@ -758,6 +725,17 @@ struct sg_engine {
     sg_param_token_req* d_preq = nullptr;
     uint64_t* d_pvals = nullptr;
     uint64_t pcap = 0, pvcap = 0;
+    // exact parameter keys (pkeys.h): the value dictionary of sg_param_intern, the entries the loaded param rules'
+    // hot items pin, and the sweep's device buffers (keysweep.hip) and statistics (sg_param_keys_stats)
+    pk::Dict<pk::StdHash> pkeys;
+    std::vector<uint64_t> par_pins;
+    uint64_t* d_ks_key = nullptr;
+    uint32_t *d_ks_idx = nullptr, *d_ks_marks = nullptr;
+    uint64_t ks_cap = 0;                          // slots of d_ks_key / d_ks_idx (and bits of d_ks_marks)
+    hipEvent_t ks_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint64_t ks_sweeps = 0, ks_last[4] = {0, 0, 0, 0};  // last sweep: candidates, held on the device, dropped, us
+    double ks_scan_ms[3] = {0, 0, 0};             // ... and its scans: maps, key ring, token server values
+    uint64_t pbm_words = 0;                       // words of d_pbm
     // snapshot scratch
     uint32_t *d_snap_cnt = nullptr, *d_snap_off = nullptr;
     sg_metric_node* d_snap_out = nullptr;
@@ -1535,6 +1513,8 @@ int sg_engine_destroy(sg_engine* e) {
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_nslimit); dfree(e->d_nsb); dfree(e->d_borrow); dfree(e->d_keyring);
     dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx); dfree(e->d_tbounds);
     dfree(e->d_snap_cnt); dfree(e->d_snap_off); dfree(e->d_snap_out); dfree(e->d_dbg);
+    dfree(e->d_ks_key); dfree(e->d_ks_idx); dfree(e->d_ks_marks);
+    for (auto& v : e->ks_ev) if (v) (void)hipEventDestroy(v);
     for (auto& B : e->slot)
         for (auto& v : B.ev) if (v) (void)hipEventDestroy(v);
     if (e->gstream) (void)hipStreamDestroy(e->gstream);
@@ -1586,6 +1566,98 @@ static int register_rule_resource(sg_engine* e, const char* name, uint32_t* id) 
     if (e->names.size() >= e->cfg.max_resources) return fail(SG_ECAPACITY, "max_resources reached");
     *id = intern(e, name);
     return SG_OK;
+}
+
+// ---- exact parameter keys (pkeys.h, keysweep.hip; the epoch rule is in the header)
+int sg_param_intern(sg_engine* e, const char* value, const char* class_type, uint64_t* out_key) {
+    if (!e || !out_key) return fail(SG_EINVAL, "null argument");
+    *out_key = e->pkeys.intern(value, class_type);
+    return SG_OK;
+}
+
+int sg_param_intern_batch(sg_engine* e, const char* const* values, const char* const* class_types, uint32_t n,
+                          uint64_t* out_keys) {
+    if (!e || (n && (!values || !out_keys))) return fail(SG_EINVAL, "null argument");
+    for (uint32_t i = 0; i < n; ++i) out_keys[i] = e->pkeys.intern(values[i], class_types ? class_types[i] : nullptr);
+    return SG_OK;
+}
+
+int sg_param_keys_sweep(sg_engine* e) {
+    if (!e) return fail(SG_EINVAL, "null engine");
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = drain(e)) return rc;  // every submitted batch: its keys are in the maps and the ring by now
+    const auto t_start = std::chrono::steady_clock::now();
+    std::vector<uint64_t> cand;
+    const uint64_t E = e->pkeys.sweep_begin(cand);
+    const uint64_t nc = cand.size();
+    std::vector<uint32_t> held((nc + 31) / 32, 0u);
+    uint64_t n_held = 0;
+    e->ks_scan_ms[0] = e->ks_scan_ms[1] = e->ks_scan_ms[2] = 0;
+    const bool dev = (e->d_pmap && !e->pmap_key.empty()) || e->d_keyring || e->d_pvtab;
+    if (nc && nc >= (1ull << 30)) return fail(SG_ECAPACITY, "too many sweep candidates for one table");
+    if (nc && dev) {
+        uint64_t slots = 16;  // a power of two, at most half full
+        while (slots < 2 * nc) slots <<= 1;
+        if (slots > e->ks_cap) {
+            dfree(e->d_ks_key); dfree(e->d_ks_idx); dfree(e->d_ks_marks);
+            e->ks_cap = 0;
+            HIPCHK(hipMalloc(&e->d_ks_key, slots * 8));
+            HIPCHK(hipMalloc(&e->d_ks_idx, slots * 4));
+            HIPCHK(hipMalloc(&e->d_ks_marks, ((slots + 31) / 32) * 4));
+            e->ks_cap = slots;
+        }
+        for (auto& v : e->ks_ev)
+            if (!v) HIPCHK(hipEventCreate(&v));
+        std::vector<uint64_t> tk(slots, PK_EMPTY);
+        std::vector<uint32_t> ti(slots, 0u);
+        for (uint64_t i = 0; i < nc; ++i) {  // the probe of keysweep.hip ks_mark
+            uint64_t h = (uint32_t)mix64(cand[i]) & (slots - 1);
+            while (tk[h] != PK_EMPTY) h = (h + 1) & (slots - 1);
+            tk[h] = cand[i];
+            ti[h] = (uint32_t)i;
+        }
+        hipStream_t st = e->stream;
+        HIPCHK(hipMemcpyAsync(e->d_ks_key, tk.data(), slots * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(e->d_ks_idx, ti.data(), slots * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(e->d_ks_marks, 0, held.size() * 4, st));
+        HIPCHK(launch_keysweep(e->pmap_key.empty() ? nullptr : e->d_pmap, (uint32_t)e->pmap_key.size(), e->d_pbkt,
+                               e->pool_nb, e->d_pbm, e->pbm_words, e->d_keyring,
+                               e->d_keyring ? 1ull << e->cfg.status_ring_log2 : 0, e->d_pvtab,
+                               e->d_pvtab ? (uint64_t)e->pv_mask + 1 : 0, e->d_ks_key, e->d_ks_idx,
+                               (uint32_t)(slots - 1), e->d_ks_marks, e->ks_ev, st));
+        HIPCHK(hipMemcpyAsync(held.data(), e->d_ks_marks, held.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, e->ks_ev[k], e->ks_ev[k + 1]) == hipSuccess) e->ks_scan_ms[k] = ms;
+        }
+        (void)hipGetLastError();
+        for (uint32_t w : held) n_held += (uint64_t)__builtin_popcount(w);
+    }
+    // (a failure above leaves the epoch opened and drops nothing: the candidates are candidates again next time)
+    const uint64_t dropped = e->pkeys.sweep_finish(E, cand, held.data());
+    ++e->ks_sweeps;
+    e->ks_last[0] = nc;
+    e->ks_last[1] = n_held;
+    e->ks_last[2] = dropped;
+    e->ks_last[3] = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_start).count();
+    return SG_OK;
+}
+
+int sg_param_keys_stats(sg_engine* e, uint64_t* out, int cap) {
+    if (!e || !out) return 0;
+    const pk::Stats s = e->pkeys.stats();
+    const uint64_t v[8] = {s.entries, s.displaced, s.pinned, e->ks_sweeps, e->ks_last[0], e->ks_last[1], e->ks_last[2],
+                           e->ks_last[3]};
+    int k = 0;
+    for (; k < cap && k < 8; ++k) out[k] = v[k];
+    return k;
+}
+// diagnostics export: the last sweep's scans in ms {maps, key ring, token server values}
+extern "C" int sgx_keysweep_scans(sg_engine* e, double* out) {
+    if (!e || !out) return -1;
+    for (int k = 0; k < 3; ++k) out[k] = e->ks_scan_ms[k];
+    return 0;
 }
 
 // FlowRuleManager.loadRules -> FlowRuleUtil.buildFlowRuleMap (core/slots/block/flow/FlowRuleUtil.java:89-137)
@@ -2101,6 +2173,7 @@ static int rebuild_pmaps(sg_engine* e, const std::map<uint32_t, uint32_t>& rcap,
     e->d_tmid = nt;
     e->n_pslot = total;
     e->pool_nb = pool_nb;
+    e->pbm_words = nbkt ? nword : 0;
     {
         const unsigned long long next[2] = {nbkt, nbkt};  // PC_NEXT, PC_FLOOR
         HIPCHK(hipMemcpy(e->d_pool_next, next, 16, hipMemcpyHostToDevice));
@@ -2151,9 +2224,28 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
     if (int rc = drain(e)) return rc;  // no batch in flight while the rule tables change
     std::vector<ParamR> all;
     std::vector<std::string> keys;
+    // Hot items (local and cluster rules alike) are interned through the dictionary and pinned: the list's pins
+    // replace the last list's once the load has succeeded.  A load that fails before anything changed gives its
+    // pins back; one that fails later keeps both lists' pins (a pinned entry too many is never a wrong key).
+    struct Pins {
+        sg_engine* e;
+        std::vector<uint64_t> now;
+        int end = 0;  // 0: give back, 1: keep beside the old ones, 2: replace the old ones
+        ~Pins() {
+            if (end == 0) for (uint64_t k : now) e->pkeys.unpin(k);
+            else if (end == 1) e->par_pins.insert(e->par_pins.end(), now.begin(), now.end());
+            else { for (uint64_t k : e->par_pins) e->pkeys.unpin(k); e->par_pins = std::move(now); }
+        }
+    } pins{e, {}};
+    auto item_key = [&](const char* v, const char* t) {
+        bool entry = false;
+        const uint64_t k = e->pkeys.intern(v, t, true, &entry);
+        if (entry) pins.now.push_back(k);
+        return k;
+    };
     for (uint32_t i = 0; i < n; ++i) {
         if (rules[i].n_items > 0 && !rules[i].items) return fail(SG_EINVAL, "param rule items pointer is null");
-        all.push_back(make_param(rules[i]));
+        all.push_back(make_param(rules[i], item_key));
         keys.push_back(all.back().eqkey);
     }
     // a negative paramIdx is rewritten in the loaded rule objects (ParamFlowSlot.applyRealParamIdx), so the
@@ -2226,6 +2318,7 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
                                       std::to_string(e->cfg.param_table_log2) + " allows " +
                                       std::to_string(1ull << e->cfg.param_table_log2));
     if (int rc = rebuild_cluster_param(e, rules, all, n)) return rc;
+    pins.end = 1;  // the token server reads the new hot items from here on
     if (int rc = rebuild_pmaps(e, rcap, tmaps)) return rc;
     e->psid_of = std::move(psid_of);
     e->next_psid = next_psid;
@@ -2246,6 +2339,7 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
     }
     e->last_par = keys;
     e->par_loaded = true;
+    pins.end = 2;
     if (!e->params.empty() && !e->d_keyring) {  // thread counts can exist from now on: remember ENTRY keys
         const uint64_t nk = 1ull << e->cfg.status_ring_log2;
         HIPCHK(hipMalloc(&e->d_keyring, nk * sizeof(uint64_t)));

@@ -19,6 +19,10 @@ resources, still no data-path traffic.  Two exchanges remain, and they live here
   could go to different ranks; this module still sends all of them to one token-server rank (routing
   by namespace is the follow-up).  A namespace's request rate is bounded by its own
   limiter, so one GPU is plenty for it.
+
+Parameter keys that cross ranks (the values of a param token request, an event routed to its shard) are the
+pure function's (``sg_param_key``), the same word on every rank.  The exact keys of ``sg_param_intern`` belong
+to the engine whose dictionary gave them and must not be sent to another rank's engine.
 """
 from __future__ import annotations
 

@@ -26,7 +26,8 @@ EXPORTS = (
     "sg_cluster_request_tokens", "sg_cluster_request_param_tokens", "sg_read_node", "sg_last_error", "sg_last_timings",
     "sg_submit_ex", "sg_submit_ex_async", "sg_intern_origin", "sg_intern_context", "sg_param_thread_count",
     "sg_cluster_namespace", "sg_cluster_assign_flows", "sg_cluster_set_namespace_connected",
-    "sg_cluster_namespace_qps", "sg_load_authority_rules",
+    "sg_cluster_namespace_qps", "sg_load_authority_rules", "sg_param_intern", "sg_param_intern_batch",
+    "sg_param_keys_sweep", "sg_param_keys_stats",
 )
 
 
@@ -53,6 +54,11 @@ def lib():
         L.sg_load_param_rules.argtypes = [P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.sg_load_authority_rules.argtypes = [P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.sg_param_key.argtypes = [P, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
+        L.sg_param_intern.argtypes = [P, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
+        L.sg_param_intern_batch.argtypes = [P, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint32,
+                                            C.POINTER(C.c_uint64)]
+        L.sg_param_keys_sweep.argtypes = [P]
+        L.sg_param_keys_stats.argtypes = [P, C.POINTER(C.c_uint64), C.c_int]
         L.sg_submit.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p]
         L.sg_submit_async.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p]
         L.sg_sync.argtypes = [P]
@@ -156,6 +162,52 @@ class Engine:
     def load_authority_rules(self, rules) -> int:
         """AuthorityRuleManager.loadRules: A.authority_rule(...) list (empty: clear); returns the rules kept."""
         return self._load(lib().sg_load_authority_rules, rules, A.SgAuthorityRule)
+
+    # ---- exact parameter keys (sg_param_intern: equal keys only for equal values; keys belong to this engine)
+    def param_intern(self, value, class_type="java.lang.String") -> int:
+        """The value's key from the engine's dictionary: param_key()'s word unless another live value owns it.
+        Callable from any thread.  See include/sentinel_gpu.h for how long a key may be used (the epoch rule)."""
+        out = C.c_uint64()
+        _check(lib().sg_param_intern(self.h, None if value is None else str(value).encode(),
+                                     None if class_type is None else class_type.encode(), C.byref(out)))
+        return out.value
+
+    def param_intern_many(self, values, class_types="java.lang.String") -> np.ndarray:
+        """sg_param_intern_batch: values (str / bytes / None each) with one class type for all, or one each."""
+        n = len(values)
+        enc = [v if v is None or isinstance(v, bytes) else str(v).encode() for v in values]
+        vals = (C.c_char_p * max(1, n))(*enc)
+        if class_types is None or isinstance(class_types, str):
+            ct = None if class_types is None else class_types.encode()
+            types = (C.c_char_p * max(1, n))(*([ct] * n))
+        else:
+            types = (C.c_char_p * max(1, n))(*[None if t is None else t.encode() for t in class_types])
+        out = np.zeros(n, dtype=np.uint64)
+        _check(lib().sg_param_intern_batch(self.h, vals, types, n, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def param_keys_sweep(self) -> dict:
+        """sg_param_keys_sweep: drop the dictionary entries the device no longer holds; returns param_keys_stats().
+        Waits for every submitted batch; call it from the submitting thread."""
+        _check(lib().sg_param_keys_sweep(self.h))
+        return self.param_keys_stats()
+
+    def param_keys_stats(self) -> dict:
+        out = (C.c_uint64 * 8)()
+        k = lib().sg_param_keys_stats(self.h, out, 8)
+        names = ("entries", "displaced", "pinned", "sweeps", "candidates", "held", "dropped", "sweep_us")
+        return {names[i]: int(out[i]) for i in range(k)}
+
+    def keysweep_scans(self):
+        """The last sweep's device scans in ms: (maps, key ring, token server values); diagnostics export
+        sgx_keysweep_scans."""
+        fn = lib().sgx_keysweep_scans
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        out = (C.c_double * 3)()
+        if fn(self.h, out) != 0:
+            raise SentinelError(A.SG_EDEVICE, "sgx_keysweep_scans failed")
+        return tuple(out)
 
     # ---- decisions
     def submit(self, events: np.ndarray) -> np.ndarray:

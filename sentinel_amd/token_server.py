@@ -24,7 +24,8 @@ Reference (csrv/ = sentinel-cluster/sentinel-cluster-server-default/src/main/jav
   csrv/processor/ParamFlowRequestProcessor.java:33-52        requestParamToken -> (status, remaining, 0)
 
 PARAM_FLOW requests of a tick are decided in one `sg_cluster_request_param_tokens` call; their
-typed values are interned with the same 64-bit keys as the rules' hot items (`sg_param_key`).
+typed values are interned with the same 64-bit keys as the rules' hot items (`sg_param_key`, or exactly --
+equal keys only for equal values -- with the engine's dictionary, `param_key=eng.param_intern`).
 """
 from __future__ import annotations
 
@@ -255,13 +256,19 @@ class TokenServer:
     when given, every namespace gets a GlobalRequestLimiter of its own on the device
     (`cluster_namespace`), the flowIds of `flow_namespaces` are assigned to them (`cluster_assign_flows`)
     before the first request is served, and a ping or a disconnect makes one
-    `cluster_set_namespace_connected` call.  None: one limiter for all, and per-flow connected counts."""
+    `cluster_set_namespace_connected` call.  None: one limiter for all, and per-flow connected counts.
+    `param_key` turns (text, java class) into the 64-bit key of a PARAM_FLOW value: `engine.param_key` is the pure
+    hash, `eng.param_intern` the exact choice (two values never share a count); its dictionary is kept bounded
+    by `key_sweep_s`: when set and the service has `param_keys_sweep`, the tick loop calls it once that many
+    seconds have passed since the last sweep (0: after every tick), between device calls."""
 
     def __init__(self, service, flow_namespaces: Optional[Dict[int, str]] = None,
                  clock: Optional[Callable[[], int]] = None, max_batch: int = 65536, record: bool = False,
                  param_key: Optional[Callable[[str, str], int]] = None,
-                 namespace_qps: Optional[Dict[str, float]] = None):
+                 namespace_qps: Optional[Dict[str, float]] = None, key_sweep_s: Optional[float] = None):
         self.service = service
+        self.key_sweep_s = key_sweep_s if hasattr(service, "param_keys_sweep") else None
+        self.sweeps = 0                   # key dictionary sweeps made (observability)
         self.flow_ns = dict(flow_namespaces or {})
         self.ns_qps = None if namespace_qps is None else dict(namespace_qps)
         if self.ns_qps is not None:
@@ -352,29 +359,50 @@ class TokenServer:
         order: consecutive requests of one type form one device call (FLOW and PARAM_FLOW share the
         namespace's GlobalRequestLimiter, so the order of the calls is the order of arrival).  A device
         error fails the requests of that call (TokenResultStatus.FAIL) and the loop keeps serving."""
+        last_sweep = time.monotonic()
         while True:
-            await self._wake.wait()
+            if self.key_sweep_s:  # wake up for a sweep that falls due while no request arrives
+                try:
+                    await asyncio.wait_for(self._wake.wait(),
+                                           max(0.001, last_sweep + self.key_sweep_s - time.monotonic()))
+                except asyncio.TimeoutError:
+                    pass
+            else:
+                await self._wake.wait()
             self._wake.clear()
             await asyncio.sleep(0)  # let every readable connection queue its frames first
-            if not self._pending:
-                continue
-            now = self.clock()
-            queue, self._pending = self._pending, []
-            i = 0
-            while i < len(queue):
-                typ, j = queue[i][2], i
-                while j < len(queue) and queue[j][2] == typ and j - i < self.max_batch:
-                    j += 1
-                run = [(w, x, r) for w, x, _, r in queue[i:j]]
+            ticked = self._tick()
+            # the key dictionary's sweep, between device calls (key_sweep_s = 0: after every tick)
+            if self.key_sweep_s is not None and (ticked or self.key_sweep_s) and \
+                    time.monotonic() - last_sweep >= self.key_sweep_s:
                 try:
-                    (self._decide if typ == MSG_TYPE_FLOW else self._decide_param)(run, now)
-                except Exception as exc:  # e.g. SentinelError from the device call
+                    self.service.param_keys_sweep()
+                    self.sweeps += 1
+                except Exception as exc:
                     self.errors.append(repr(exc))
-                    for w, xid, _ in run:
-                        if not w.is_closing():
-                            w.write(encode_flow_response(xid, A.TOKEN_FAIL, 0, 0) if typ == MSG_TYPE_FLOW
-                                    else encode_param_flow_response(xid, A.TOKEN_FAIL, 0))
-                i = j
+                last_sweep = time.monotonic()
+
+    def _tick(self) -> bool:
+        if not self._pending:
+            return False
+        now = self.clock()
+        queue, self._pending = self._pending, []
+        i = 0
+        while i < len(queue):
+            typ, j = queue[i][2], i
+            while j < len(queue) and queue[j][2] == typ and j - i < self.max_batch:
+                j += 1
+            run = [(w, x, r) for w, x, _, r in queue[i:j]]
+            try:
+                (self._decide if typ == MSG_TYPE_FLOW else self._decide_param)(run, now)
+            except Exception as exc:  # e.g. SentinelError from the device call
+                self.errors.append(repr(exc))
+                for w, xid, _ in run:
+                    if not w.is_closing():
+                        w.write(encode_flow_response(xid, A.TOKEN_FAIL, 0, 0) if typ == MSG_TYPE_FLOW
+                                else encode_param_flow_response(xid, A.TOKEN_FAIL, 0))
+            i = j
+        return True
 
     def _decide(self, batch, now: int):
         reqs = np.zeros(len(batch), dtype=A.TOKEN_REQ_DTYPE)
