@@ -14,6 +14,11 @@
  * Threading: one submitting thread per engine.  Every call returns before its
  * buffers may be reused, except sg_submit_async (completion via sg_sync).
  * Errors are returned as negative status codes; sg_last_error() gives the text.
+ * An async batch's errors are reported late: what its group stage finds (a bad
+ * res_id, timestamps going back inside the batch, a bad args table) is returned
+ * by the next call that touches the engine, which then accepts no batch of its
+ * own; what its decide stage finds is returned one call later still, as before.
+ * A synchronous call reports every error of its own batch itself.
  * No exception ever crosses the ABI (the Java binding turns status codes into
  * BlockException subclasses, core/CtSph.java:157-166).
  */
@@ -399,7 +404,17 @@ int sg_param_keys_stats(sg_engine* e, uint64_t* out, int cap);
  * StatisticSlot.exit (core/slots/statistic/StatisticSlot.java:136-173) for every
  * EXIT and ClusterNode.trace (core/node/ClusterNode.java:99-106) for every TRACE,
  * in event order per resource.  ev and out may be host or device pointers
- * (device pointers avoid the PCIe copy).  sg_submit is synchronous. */
+ * (device pointers avoid the PCIe copy).  sg_submit is synchronous.
+ *
+ * sg_submit_async returns once the batch's group stage is queued; the batch is
+ * not checked yet.  The next call that touches the engine -- another submit,
+ * sg_sync, a read or a rule load -- first reads that batch's verdict.  If the
+ * batch is valid, it is handed to the decide stage and the call goes on.  If not,
+ * the call returns that batch's error and does nothing else: the invalid batch
+ * is not decided and takes no event indices, and a batch passed to that call is
+ * not accepted either, so submit it again.  Flags the decide stage raises were
+ * already reported late, by the second call after the submit; this is the same
+ * rule one stage earlier.  ev and out stay valid until sg_sync returns. */
 int sg_submit(sg_engine* e, const sg_event* ev, uint64_t n, uint32_t* out);
 int sg_submit_async(sg_engine* e, const sg_event* ev, uint64_t n, uint32_t* out);
 int sg_sync(sg_engine* e);

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <map>
 #include <set>
@@ -69,6 +70,8 @@ hipError_t launch_cold_n(uint64_t n, const uint32_t* hot_total, uint32_t* out, h
 hipError_t launch_cold_small(const uint32_t* kin, const uint32_t* vin, const uint32_t* cnt, const uint32_t* dbase,
                              uint32_t* kout, uint32_t* vout, uint32_t* words, hipStream_t st);
 uint32_t hot_max();
+hipError_t launch_grp_clear(uint32_t* bsmall, uint32_t nsmall, uint32_t* bst, uint32_t nbst, uint32_t* need,
+                            uint32_t nneed, hipStream_t st);
 hipError_t launch_seg_cold(const uint32_t* keys, uint64_t n, const uint32_t* lo, const uint32_t* sbase, uint32_t* flag,
                            uint32_t* pos, Seg* segs, hipStream_t st,
                            hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
@@ -571,13 +574,41 @@ struct sg_engine {
         Link* d_link = nullptr;        // frozen-stretch skipping side tables (DevState.link/bst/pend/spans)
         uint32_t *d_bst = nullptr, *d_pend = nullptr;
         Span* d_spans = nullptr;
-        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // group start/end, decide start/end, post end
-        bool pending = false;  // decide enqueued, not yet collected (timings, flags)
+        hipEvent_t* ev = nullptr;      // the batch's event set (evset[]): group start/end, decide start/end, post end
+        hipEvent_t last_post = nullptr;  // post end of the last batch decided from this slot: the next group stage to
+                                         // fill the slot waits for it on the device
+        uint32_t* h_head = nullptr;    // pinned: d_bsmall[0..77) as the group stage left it (copied on gstream)
+        // What the decide stage needs of the group part's locals: it may run inside the next submit, after
+        // e->gbase, e->epoch and the d_* aliases have moved on, so nothing of these is re-read from the engine.
+        struct Grouped {
+            uint64_t n = 0, n_args = 0, gbase = 0, ring_mask = 0;
+            const sg_event* dev_ev = nullptr;
+            const sg_event_ext* dev_ext = nullptr;
+            const sg_arg* dev_args = nullptr;
+            uint32_t *out = nullptr, *dev_out = nullptr, *vin = nullptr;
+            uint32_t epoch = 0, skip_min = 0, lane_max = 0, mb = 0;
+            bool ext = false, host_out = false, force_lane = false;
+            int set = 0;               // index of its event set and flag mirror
+        } g;
     } slot[2];
     int cur = 0;                 // slot of the next batch
-    int last = -1;               // slot of the last batch submitted
+    int last = -1;               // slot of the last batch handed to the decide stage
+    int grouped = -1;            // slot of a batch whose group stage is enqueued and whose head is not read yet: the
+                                 // next call that touches the engine hands it to the decide stage (handoff())
+    int held_rc = 0;             // an error a diagnostics export met while draining (it cannot return one): the next
+    std::string held_msg;        // ABI call that drains or submits returns it
+    bool handoff_late = true;    // SG_HANDOFF=0: every batch is handed off inside the call that submits it
+    // Event sets and flag mirrors rotate over four batches: the batch being grouped, the one being decided, the one
+    // being collected, and the one before that, whose end events the collected batch's gaps are measured from.
+    static constexpr int N_SETS = 4;
+    hipEvent_t evset[N_SETS][5] = {};
+    uint32_t* h_mirror = nullptr;  // pinned, N_SETS x MIRROR_WORDS: d_bsmall[0..121) as the decide stage left it
+    uint64_t seq = 0;              // batches handed to the decide stage so far (batch i has set i % N_SETS)
+    struct InFlight { int set; uint32_t hot_marked; };
+    std::deque<InFlight> inflight;  // handed off, not yet collected (timings, flags), oldest first
     hipStream_t gstream = nullptr;
     std::vector<std::array<double, 4>> tlog;  // per batch [group, decide, post, total] ms, by collect()
+    std::vector<std::array<double, 2>> glog;  // per batch [group-stream idle, decide-stream idle] ms before it
     std::string fatal;           // non-empty: a batch left device state inconsistent; every later submit fails
     uint32_t* d_prio = nullptr;  // [res] sticky PM_* marks (DevState.prio)
     // hot / cold group stage (kernels.hip k_grp_*): [sort key] -> hot id of the next batch (0xFFFF: cold), the ids'
@@ -742,6 +773,8 @@ struct sg_engine {
     uint64_t snap_cap = 0;
 };
 
+static int handoff(sg_engine* e);  // (with the batch pipeline, below)
+
 namespace {
 
 constexpr uint64_t SHARD_BATCH = 3ull << 21;  // batches of fewer events take the shard-sized bins and skip threshold
@@ -827,27 +860,42 @@ int ensure_batch(sg_engine* e, uint64_t n) {
     return SG_OK;
 }
 
-// The slot's batch: wait for its decide stage, record its stage times and check its device flags.
-static int collect(sg_engine* e, int k) {
-    auto& B = e->slot[k];
-    if (!B.pending) return SG_OK;
-    B.pending = false;
-    HIPCHK(hipEventSynchronize(B.ev[4]));
+constexpr uint32_t HEAD_WORDS = 77;     // d_bsmall words the host reads after the group stage
+constexpr uint32_t MIRROR_WORDS = 121;  // ... and after the decide stage ([0] bflags, [120] frozen spans)
+
+// The oldest batch in flight: wait for its decide stage, record its stage times and the idle time of both streams
+// before it, and check its device flags (from the pinned mirror its decide stage filled: nothing is enqueued here).
+static int collect(sg_engine* e) {
+    if (e->inflight.empty()) return SG_OK;
+    const sg_engine::InFlight f = e->inflight.front();
+    e->inflight.pop_front();
+    hipEvent_t* ev = e->evset[f.set];
+    HIPCHK(hipEventSynchronize(ev[4]));
     float g = 0, d = 0, p = 0;
-    (void)hipEventElapsedTime(&g, B.ev[0], B.ev[1]);
-    (void)hipEventElapsedTime(&d, B.ev[2], B.ev[3]);
-    (void)hipEventElapsedTime(&p, B.ev[3], B.ev[4]);
+    (void)hipEventElapsedTime(&g, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&d, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&p, ev[3], ev[4]);
     (void)hipGetLastError();
     e->last_ms[0] = g; e->last_ms[1] = d; e->last_ms[2] = p; e->last_ms[3] = (double)g + d + p;
     e->tlog.push_back({(double)g, (double)d, (double)p, (double)g + d + p});
     if (e->tlog.size() > 4096) e->tlog.erase(e->tlog.begin(), e->tlog.begin() + 2048);
-    uint32_t bflags = 0;  // on gstream: a null-stream copy could share a queue with a decide kernel
-    HIPCHK(hipMemcpyAsync(&bflags, B.d_bsmall, 4, hipMemcpyDeviceToHost, e->gstream));
-    uint32_t nspan = 0;
-    HIPCHK(hipMemcpyAsync(&nspan, B.d_bsmall + 120, 4, hipMemcpyDeviceToHost, e->gstream));
-    HIPCHK(hipStreamSynchronize(e->gstream));
-    e->spans_total += nspan;
-    e->hot_marked_last = B.hot_marked;
+    // the gaps: from the end events of the batch handed off before this one (its set is intact: N_SETS); the
+    // engine's first batch has none
+    float ga = 0, gb = 0;
+    const uint64_t collected = e->seq - e->inflight.size() - 1;  // batches handed off before this one
+    if (collected > 0) {
+        hipEvent_t* pv = e->evset[(f.set + sg_engine::N_SETS - 1) % sg_engine::N_SETS];
+        // as measured: a wrong pairing of event sets shows as a negative gap or, where an event was not recorded, NaN
+        if (hipEventElapsedTime(&ga, pv[1], ev[0]) != hipSuccess) ga = NAN;
+        if (hipEventElapsedTime(&gb, pv[4], ev[2]) != hipSuccess) gb = NAN;
+        (void)hipGetLastError();
+    }
+    e->glog.push_back({(double)ga, (double)gb});
+    if (e->glog.size() > 4096) e->glog.erase(e->glog.begin(), e->glog.begin() + 2048);
+    const uint32_t* mir = e->h_mirror + (size_t)f.set * MIRROR_WORDS;
+    const uint32_t bflags = mir[0];
+    e->spans_total += mir[120];
+    e->hot_marked_last = f.hot_marked;
     // Flags the decide kernels raise (the group stage's own checks return before the decide stage runs):
     // an EXIT/TRACE whose reference names an event that is not an earlier ENTRY of its resource, and a
     // batch starting before the last window a resource already holds (the clock went back).
@@ -874,14 +922,25 @@ static int collect(sg_engine* e, int k) {
 static inline const AuthDesc* dev_auth(const sg_engine* e) { return e->auth_on ? e->d_auth : nullptr; }
 static inline const uint32_t* dev_auth_ids(const sg_engine* e) { return e->auth_on ? e->d_auth_ids : nullptr; }
 
+// A batch that is grouped and not handed off yet gets its verdict and its decide stage here first, so every call
+// but an async submit leaves no batch behind.  The first error wins; the later batches are still collected.
 static int drain(sg_engine* e) {
-    int rc = SG_OK;
-    for (int i = 0; i < 2; ++i) {  // oldest first
-        int r = collect(e, (e->cur + i) & 1);
-        if (r && !rc) rc = r;
-    }
+    int rc = e->held_rc;
+    std::string msg = e->held_msg;
+    e->held_rc = 0;
+    auto note = [&](int r) {
+        if (r && !rc) { rc = r; msg = g_err; }
+    };
+    note(handoff(e));
+    while (!e->inflight.empty()) note(collect(e));  // oldest first
     HIPCHK(hipStreamSynchronize(e->stream));
-    return rc;
+    return rc ? fail(rc, msg) : SG_OK;
+}
+// drain() for the diagnostics exports, which have no way to return an error: an async batch's verdict met here is
+// kept for the next ABI call, not swallowed
+static void drain_hold(sg_engine* e) {
+    const int rc = drain(e);
+    if (rc) { e->held_rc = rc; e->held_msg = g_err; }
 }
 
 
@@ -1305,8 +1364,15 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (hipStreamCreateWithPriority(&e->gstream, hipStreamNonBlocking, prio_lo) != hipSuccess) {
         return bad(fail(SG_EDEVICE, "stream"));
     }
-    for (auto& B : e->slot)
-        for (auto& v : B.ev) if (hipEventCreate(&v) != hipSuccess) return bad(fail(SG_EDEVICE, "event"));
+    for (auto& s : e->evset)
+        for (auto& v : s) if (hipEventCreate(&v) != hipSuccess) return bad(fail(SG_EDEVICE, "event"));
+    for (auto& B : e->slot) {
+        if (hipHostMalloc(&B.h_head, HEAD_WORDS * 4) != hipSuccess) return bad(fail(SG_ENOMEM, "pinned batch head"));
+        B.ev = e->evset[0];
+    }
+    if (hipHostMalloc(&e->h_mirror, sg_engine::N_SETS * MIRROR_WORDS * 4) != hipSuccess)
+        return bad(fail(SG_ENOMEM, "pinned batch flags"));
+    std::memset(e->h_mirror, 0, sg_engine::N_SETS * MIRROR_WORDS * 4);
     uint64_t R = cfg.max_resources;
     if (hipMalloc(&e->d_sec, R * 2 * sizeof(Bkt)) != hipSuccess || hipMalloc(&e->d_minb, R * 60 * sizeof(Bkt)) != hipSuccess ||
         hipMalloc(&e->d_info, R * sizeof(NodeInfo)) != hipSuccess || hipMalloc(&e->d_prog, R * sizeof(Prog)) != hipSuccess ||
@@ -1353,6 +1419,7 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (const char* v = std::getenv("SG_HEAD_MIN")) e->head_min = (uint32_t)std::strtoul(v, nullptr, 0);
     if (const char* v = std::getenv("SG_J4_MAX")) { e->j4_max = (uint32_t)std::strtoul(v, nullptr, 0); e->bins_pinned = true; }
     if (const char* v = std::getenv("SG_PIPELINE")) e->pipeline = v[0] == '1';
+    if (const char* v = std::getenv("SG_HANDOFF")) e->handoff_late = v[0] != '0';
     if (const char* v = std::getenv("SG_TINY")) e->tiny_on = v[0] != '0';
     if (const char* v = std::getenv("SG_LITE_CHECK")) { if (v[0] == '1') e->dbg_flags |= LITE_CHECK; }
     if (const char* v = std::getenv("SG_RADIX_BELOW")) e->radix_below = std::strtoull(v, nullptr, 0);
@@ -1387,30 +1454,42 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
 // 4 doubles each ([group, decide, post, total] ms); returns the number of batches written
 extern "C" int sgx_timing_log(sg_engine* e, double* out, int cap) {
     if (!e || !out) return 0;
-    (void)drain(e);
+    drain_hold(e);
     int k = 0;
     for (; k < cap && k < (int)e->tlog.size(); ++k)
         for (int j = 0; j < 4; ++j) out[4 * k + j] = e->tlog[k][j];
     e->tlog.clear();
     return k;
 }
+// diagnostics export (not part of the ABI): for the batches collected since the last call, how long each stream stood
+// empty before the batch, 2 doubles each: [group stream: the previous batch's group end to this batch's group start,
+// decide stream: the previous batch's post end to this batch's decide start] ms; 0 for the engine's first batch
+extern "C" int sgx_gap_log(sg_engine* e, double* out, int cap) {
+    if (!e || !out) return 0;
+    drain_hold(e);
+    int k = 0;
+    for (; k < cap && k < (int)e->glog.size(); ++k)
+        for (int j = 0; j < 2; ++j) out[2 * k + j] = e->glog[k][j];
+    e->glog.clear();
+    return k;
+}
 // diagnostics export (not part of the ABI): frozen span slots recorded by the cooperative kernels so far
 extern "C" unsigned long long sgx_spans_total(sg_engine* e) {
     if (!e) return 0;
-    (void)drain(e);
+    drain_hold(e);
     return e->spans_total;
 }
 // diagnostics export: hot ids whose side tables the last collected batch built (0 on the radix stage and with
 // SG_DEBUG_FLAGS & 32768, which build them everywhere)
 extern "C" unsigned int sgx_hot_marked(sg_engine* e) {
     if (!e) return 0;
-    (void)drain(e);
+    drain_hold(e);
     return e->hot_marked_last;
 }
 // diagnostics export: zero the SG_DEBUG counters ([20] is a running minimum)
 extern "C" int sgx_debug_reset(sg_engine* e) {
     if (!e || !e->d_dbg) return 0;
-    (void)drain(e);
+    drain_hold(e);
     unsigned long long z[64] = {0};
     z[20] = ~0ull;
     return hipMemcpy(e->d_dbg, z, sizeof(z), hipMemcpyHostToDevice) == hipSuccess ? 1 : 0;
@@ -1497,6 +1576,8 @@ static void free_pv(sg_engine* e);
 int sg_engine_destroy(sg_engine* e) {
     if (!e) return SG_OK;
     (void)hipSetDevice(e->device);
+    // a batch that is grouped and not handed off is dropped: its group stage ends by itself, nothing waits for it
+    e->grouped = -1;
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->gstream) (void)hipStreamSynchronize(e->gstream);
     dfree(e->d_sec); dfree(e->d_minb); dfree(e->d_info); dfree(e->d_prog); dfree(e->d_rules); dfree(e->d_rstate);
@@ -1515,8 +1596,10 @@ int sg_engine_destroy(sg_engine* e) {
     dfree(e->d_snap_cnt); dfree(e->d_snap_off); dfree(e->d_snap_out); dfree(e->d_dbg);
     dfree(e->d_ks_key); dfree(e->d_ks_idx); dfree(e->d_ks_marks);
     for (auto& v : e->ks_ev) if (v) (void)hipEventDestroy(v);
-    for (auto& B : e->slot)
-        for (auto& v : B.ev) if (v) (void)hipEventDestroy(v);
+    for (auto& s : e->evset)
+        for (auto& v : s) if (v) (void)hipEventDestroy(v);
+    for (auto& B : e->slot) if (B.h_head) (void)hipHostFree(B.h_head);
+    if (e->h_mirror) (void)hipHostFree(e->h_mirror);
     if (e->gstream) (void)hipStreamDestroy(e->gstream);
     for (auto& v : e->join) if (v) (void)hipEventDestroy(v);
     if (e->fork) (void)hipEventDestroy(e->fork);
@@ -2467,36 +2550,21 @@ static bool is_device_ptr(const void* p) {
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-// Batch pipeline: the group stage (records, sort, segments, bins) of this batch runs on gstream and
-// the host waits for it only; the decide stage (reference resolution, chain grants, decide kernels,
-// post) is enqueued on stream behind the previous batch's and the call returns.  So batch k+1's
-// group stage overlaps batch k's decide stage.  Buffers must stay valid until sg_sync.
-static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext, uint64_t n, const sg_arg* args,
-                       uint64_t n_args, uint32_t* out) {
-    if (!e || (n && (!ev || !out))) return fail(SG_EINVAL, "null argument");
-    if (n_args && !args) return fail(SG_EINVAL, "null args table");
-    if (!e->fatal.empty()) return fail(SG_ESTATE, e->fatal + " -- engine unusable, recreate it");
-    if (n == 0) return SG_OK;
-    if (n > e->cfg.max_batch_events || n >= (1ull << 31)) return fail(SG_EINVAL, "batch larger than max_batch_events");
-    HIPCHK(hipSetDevice(e->device));
-    int rc = ensure_batch(e, n);
-    if (rc) return rc;
-    const int k = e->cur;
-    rc = collect(e, k);  // the batch that last used this slot (two batches ago) is decided
-    if (rc) return rc;
-    // the param map pool: the regions maps grew out of are dropped by a compaction between batches once the growth
-    // since the last one took half of what was free (the counts are a batch or two old); a batch that finds the pool
-    // short before that compacts on the device itself (launch_pm_grow)
-    if (int prc = ensure_pool2(e)) return prc;
-    const unsigned long long pfloor = e->h_pool_next ? e->h_pool_next[PC_FLOOR] : 0;
-    if (e->pool_nb && e->h_pool_next[PC_NEXT] > pfloor + (e->pool_nb - pfloor) / 2) {
-        if (int drc = drain(e)) return drc;
-        if (int crc = compact_pmaps(e)) return crc;
-        ++e->n_compact;
-    }
+static int decide_stage(sg_engine* e, int k);
+
+// The group stage (records, sort, segments, bins) of a batch, enqueued on gstream into slot k; it ends with the copy
+// of the batch's head into the slot's pinned buffer and the group-end event.  Its first kernel (k_grp_first /
+// k_rs_first) runs long enough for the host to enqueue a whole decide stage behind it: the decide stage of slot
+// `prev` (-1: none), whose head the caller has read, is enqueued right after that kernel, so gstream never waits
+// for the host to get through those launches.  What the decide stage of this batch needs is left in B.g.
+static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_ext* ext, uint64_t n, const sg_arg* args,
+                       uint64_t n_args, uint32_t* out, int* prev) {
     activate(e, k);
     auto& B = e->slot[k];
-    hipStream_t gs = e->gstream, st = e->stream;
+    B.ev = e->evset[e->seq % sg_engine::N_SETS];
+    hipStream_t gs = e->gstream;
+    // the slot's last batch is decided and its decisions are out before anything of the slot is overwritten
+    if (B.last_post) HIPCHK(hipStreamWaitEvent(gs, B.last_post, 0));
     const sg_event* dev_ev = ev;
     bool host_in = !is_device_ptr(ev);
     bool host_out = !is_device_ptr(out);
@@ -2530,8 +2598,8 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     // Overlapping this group stage with the previous batch's decide stage wins once the decide kernels
     // no longer stream frozen stretches through single CUs (C4 on MI355X: 6.45 -> 5.45 ms per batch);
     // SG_PIPELINE=0 runs the stages back to back.
-    if (!e->pipeline && e->last >= 0 && e->slot[e->last].pending)
-        HIPCHK(hipStreamWaitEvent(gs, e->slot[e->last].ev[4], 0));
+    if (!e->pipeline && e->last >= 0 && e->slot[e->last].last_post)
+        HIPCHK(hipStreamWaitEvent(gs, e->slot[e->last].last_post, 0));
     HIPCHK(hipEventRecord(B.ev[0], gs));
     // ---- 1. group: records + stable LSD radix sort on res_id (8-bit digits over the bits of max_resources-1)
     uint32_t R = e->cfg.max_resources;
@@ -2543,13 +2611,16 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     const int db = 8;
     int passes = (bits + db - 1) / db;
     uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
-    HIPCHK(hipMemsetAsync(e->d_bsmall, 0, 256 * 4, gs));
     int64_t* d_t0 = reinterpret_cast<int64_t*>(e->d_bsmall + 4);  // [4..5]
     uint32_t *kin = e->d_k1, *vin = e->d_v1, *kout = e->d_k0, *vout = e->d_v0;
     if (++e->epoch == 0) e->epoch = 1;
     // every event through the radix passes: SG_DEBUG_FLAGS & 8192 (A/B of the group stage), or a batch of 2^30 events
     // or more (the hot / cold stage's words hold a position in 30 bits)
     B.radix = e->radix_group || n >= (1ull << 30) || n < e->radix_below;
+    // one launch clears the batch's small words and, for the hot / cold stage, bst[] and the side-table marks: the
+    // slot's are free once its last batch is decided (above), d_need since the previous group stage on this stream
+    HIPCHK(launch_grp_clear(e->d_bsmall, 256, e->d_bst, B.radix ? 0u : (uint32_t)((n + 1023) / 1024), e->d_need,
+                            B.radix ? 0u : (uint32_t)e->need_words, gs));
     // bins + bin-ordered dispatch list (per-block counts -> scan -> placement), sized by an upper bound of
     // the segment count so that the group stage needs one host round trip
     const bool force_lane = !e->cfg.switch_on || (e->dbg_flags & 2);
@@ -2598,10 +2669,21 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         HIPCHK(launch_seg_order(e->d_segs, e->d_bsmall + 1, mb, e->d_blkcnt, e->d_order, e->d_bsmall + 8, gs));
         return SG_OK;
     };
+    // the previous batch's decide stage, enqueued while this batch's first kernel runs; the d_* aliases come back
+    // to this slot afterwards
+    auto decide_prev = [&]() -> int {
+        if (*prev < 0) return SG_OK;
+        const int pk = *prev;
+        *prev = -1;  // (enqueued, or failed for good: the caller does not try again)
+        const int drc = decide_stage(e, pk);
+        activate(e, k);
+        return drc;
+    };
     if (B.radix) {
         HIPCHK(launch_rs_first(dev_ev, n, R, e->gbase, e->d_ring, ring_mask, e->cfg.statistic_max_rt, e->d_rec_o,
                                e->d_k1, e->d_v1, e->d_hist, nblocks, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
                                e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e), gs));
+        if (int drc = decide_prev()) return drc;
         for (int p = 0; p < passes; ++p) {
             if (p > 0) HIPCHK(launch_radix_hist(kin, n, p * db, e->d_hist, nblocks, gs));
             HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks << db, e->d_part, nullptr, gs));
@@ -2628,6 +2710,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
                                 e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e),
                                 e->d_hot_tab, nhot, nblocks,
                                 words, hot_off, e->d_k1, e->d_v1, ccnt, e->d_hist, gs));
+        if (int drc = decide_prev()) return drc;
         HIPCHK(launch_hot_scan(hot_off, nblocks, nhot, e->d_hot_part, e->d_hot_hb, e->d_bsmall + 77, gs));
         HIPCHK(launch_cold_n(n, e->d_bsmall + 77, e->d_bsmall + 78, gs));
         if (nblocks == 1) {  // one tile: the cold pairs sorted by one workgroup (k_cold_small), into k0 / v0
@@ -2650,7 +2733,6 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         const uint64_t sc = nblocks + 64;
         HIPCHK(launch_seg_cold(kin, n, e->d_bsmall + 77, e->d_bsmall + 80, ccnt + sc, ccnt + 2 * sc, e->d_segs, gs,
                                launch_scan, e->d_part, e->d_bsmall + 82, e->d_bsmall + 1));
-        HIPCHK(hipMemsetAsync(e->d_bst, 0, ((n + 1023) / 1024) * 4, gs));
         // the bins first: they read only the segments, the programs and the marks of k_grp_first, and say which
         // side tables the record kernels must build (SG_DEBUG_FLAGS & 32768: all of them, as the radix stage does)
         uint32_t *need_hot = nullptr, *need_blk = nullptr, *bmax = nullptr;
@@ -2658,7 +2740,6 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
             need_hot = e->d_need;
             need_blk = e->d_need + hot_max();
             bmax = e->d_need + e->need_words - hot_max();
-            HIPCHK(hipMemsetAsync(e->d_need, 0, e->need_words * 4, gs));
             HIPCHK(launch_hot_bmax(dev_ev, nblocks, hot_off, nhot, e->d_hot_hb, e->d_edges, bmax, gs));
         }
         if (int brc = bins(need_hot, need_blk, bmax)) return brc;
@@ -2677,18 +2758,34 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
                                 e->d_bsmall + 76, gs));
     // [0] bflags [1] nseg [3] nprev [4..5] t0 [6..7] XF_MIX lists [8..8+N_BINS] bin offsets [72] wide XF_MIX events
     // [73] hot ids marked for the side tables [76] the next batch's hot ids
-    uint32_t head[77];
-    static_assert(8 + N_BINS + 1 <= 72, "head layout");
-    HIPCHK(hipMemcpyAsync(head, e->d_bsmall, sizeof(head), hipMemcpyDeviceToHost, gs));
+    static_assert(8 + N_BINS + 1 <= 72 && HEAD_WORDS == 77, "head layout");
+    HIPCHK(hipMemcpyAsync(B.h_head, e->d_bsmall, HEAD_WORDS * 4, hipMemcpyDeviceToHost, gs));
     HIPCHK(hipEventRecord(B.ev[1], gs));
-    HIPCHK(hipStreamSynchronize(gs));
+    auto& G = B.g;
+    G.n = n; G.n_args = n_args; G.gbase = e->gbase; G.ring_mask = ring_mask;
+    G.dev_ev = dev_ev; G.dev_ext = dev_ext; G.dev_args = dev_args;
+    G.out = out; G.dev_out = dev_out; G.vin = vin;
+    G.epoch = e->epoch; G.skip_min = skip_min; G.lane_max = lane_max; G.mb = mb;
+    G.ext = ext != nullptr; G.host_out = host_out; G.force_lane = force_lane;
+    G.set = (int)(e->seq % sg_engine::N_SETS);
+    e->grouped = k;
+    return SG_OK;
+}
+
+// The grouped batch's verdict (handoff step 1): wait for its group stage, read its head and run the group stage's
+// checks.  A batch that passes is accepted -- gbase, the slot and the event set move on -- and its decide stage is
+// the caller's to enqueue; one that fails is dropped as if its submit had returned the error.  Either way no batch is
+// left grouped.  drop: the caller gives the batch up; only the hot ids it left for the next group stage are taken.
+static int accept_grouped(sg_engine* e, bool drop = false) {
+    const int k = e->grouped;
+    auto& B = e->slot[k];
+    e->grouped = -1;
+    HIPCHK(hipEventSynchronize(B.ev[1]));
+    const uint32_t* head = B.h_head;
     if (!B.radix) e->nhot = std::min<uint32_t>(head[76], hot_max());
+    if (drop) return SG_OK;
     B.hot_marked = head[73];
-    const uint32_t m = head[1];
-    const uint32_t nprev = head[3];
-    int64_t t0 = 0;
-    std::memcpy(&t0, head + 4, 8);
-    uint32_t bflags = head[0];
+    const uint32_t bflags = head[0];
     if (bflags & BF_BAD_RES) return fail(SG_EINVAL, "event res_id >= max_resources");
     if (bflags & BF_BAD_REF)
         return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
@@ -2696,6 +2793,64 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     if (bflags & BF_BACKWARD) return fail(SG_EINVAL, "event timestamps must be non-decreasing (SURVEY Q3)");
     if (bflags & BF_BAD_ARGS)
         return fail(SG_EINVAL, "an sg_event_ext names args outside the table (or more than SG_MAX_ARGS, or a bad kind)");
+    // the decide stage's only allocation (the value-parallel passes' scratch) before the batch is counted: past
+    // this point nothing but a device error can keep its decide stage from being enqueued
+    if (e->has_mix && head[7] && (e->pv_on || e->pvt_on) && head[72]) {
+        if (int prc = ensure_pv(e, head[72], head[7])) return prc;
+    }
+    e->inflight.push_back({B.g.set, B.hot_marked});
+    ++e->seq;
+    e->last = k;
+    e->cur = k ^ 1;
+    e->gbase += B.g.n;
+    return SG_OK;
+}
+
+// A grouped batch handed to the decide stage at once (every call but an async submit starts with this: drain()).
+static int handoff(sg_engine* e) {
+    if (e->grouped < 0) return SG_OK;
+    const int k = e->grouped;
+    if (int rc = accept_grouped(e)) return rc;
+    return decide_stage(e, k);
+}
+
+static int decide_enqueue(sg_engine* e, int k);
+
+// The decide stage of the accepted batch in slot k.  The batch is counted already (accept_grouped), so a decide
+// stage that could not be enqueued whole -- a device error -- leaves the engine inconsistent: it refuses every later
+// batch, and the batch is not collected (its end events were never recorded).
+static int decide_stage(sg_engine* e, int k) {
+    const int rc = decide_enqueue(e, k);
+    if (rc) {
+        const std::string why = g_err;
+        if (!e->inflight.empty()) e->inflight.pop_back();
+        if (e->fatal.empty()) e->fatal = "the decide stage of an accepted batch could not be enqueued (" + why + ")";
+        return fail(rc, why);
+    }
+    return rc;
+}
+
+// The decide stage proper (reference resolution, chain grants, decide kernels, post), enqueued on the decide streams
+// behind the previous batch's.
+static int decide_enqueue(sg_engine* e, int k) {
+    activate(e, k);
+    auto& B = e->slot[k];
+    const auto& G = B.g;
+    hipStream_t st = e->stream;
+    const uint64_t n = G.n, n_args = G.n_args, ring_mask = G.ring_mask;
+    const sg_event* dev_ev = G.dev_ev;
+    const sg_event_ext* dev_ext = G.dev_ext;
+    const sg_arg* dev_args = G.dev_args;
+    uint32_t *out = G.out, *dev_out = G.dev_out, *vin = G.vin;
+    const uint32_t skip_min = G.skip_min, lane_max = G.lane_max, mb = G.mb;
+    const bool ext = G.ext, host_out = G.host_out, force_lane = G.force_lane;
+    (void)n_args;
+    const uint32_t* head = B.h_head;  // (the slot's next group stage, which refills it, is enqueued after this returns)
+    const uint32_t m = head[1];
+    const uint32_t nprev = head[3];
+    int64_t t0 = 0;
+    std::memcpy(&t0, head + 4, 8);
+    const uint32_t bflags = head[0];
     const uint32_t* off = head + 8;
     uint32_t bin_n[N_BINS];
     for (int b = 0; b < N_BINS; ++b) bin_n[b] = off[b + 1] - off[b];
@@ -2730,14 +2885,14 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     S.borrow = e->d_borrow;
     S.prio = e->d_prio;
     S.key_ring = e->d_keyring;
-    S.gbase = e->gbase;
+    S.gbase = G.gbase;
     S.link = e->d_link;
     S.bst = e->d_bst;
     S.pend = e->d_pend;
     S.spans = e->d_spans;
     S.nspan = e->d_bsmall + 120;
     S.span_cap = e->span_cap;
-    S.epoch = e->epoch;
+    S.epoch = G.epoch;
     S.skip_ok = !(bflags & (BF_MULTI_LINK | BF_ZERO_CNT)) && !(e->dbg_flags & 4) ? 1u : 0u;
     S.skip_min = skip_min;  // (the bins marked the side tables by it)
     S.ext = dev_ext;
@@ -2825,7 +2980,7 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
         const uint32_t nm = (uint32_t)e->pmap_key.size();
         HIPCHK(launch_pm_grow(e->d_segs, e->d_bsmall + 1, mb, Sg, e->d_pool_next, e->pool_nb, e->d_bsmall + 0, e->d_pmoves,
                               e->d_pmoves ? reinterpret_cast<uint32_t*>(e->d_pmoves + e->pmoves_cap) : nullptr,
-                              (uint32_t)e->pmoves_cap, e->epoch, nm, e->d_pbkt2, e->d_pdat2, e->d_pcwork,
+                              (uint32_t)e->pmoves_cap, G.epoch, nm, e->d_pbkt2, e->d_pdat2, e->d_pcwork,
                               e->d_pcwork + e->pmoves_cap, e->d_pcwork + 2 * e->pmoves_cap, launch_scan, st));
         HIPCHK(hipMemcpyAsync(e->h_pool_next, e->d_pool_next, PC_WORDS * 8, hipMemcpyDeviceToHost, st));
     }
@@ -2964,14 +3119,88 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
                           e->d_bsmall + 0, st));
     HIPCHK(hipEventRecord(B.ev[3], st));
     // ---- 4. decisions back to submission order + status ring
-    if (B.radix) HIPCHK(launch_post(e->d_posof, e->d_dec, n, e->gbase, e->d_ring, ring_mask, dev_out, st));
-    else HIPCHK(launch_post_w(e->d_flag, e->d_pos, B.nhot, e->d_dec, n, e->gbase, e->d_ring, ring_mask, dev_out, st));
+    if (B.radix) HIPCHK(launch_post(e->d_posof, e->d_dec, n, G.gbase, e->d_ring, ring_mask, dev_out, st));
+    else HIPCHK(launch_post_w(e->d_flag, e->d_pos, B.nhot, e->d_dec, n, G.gbase, e->d_ring, ring_mask, dev_out, st));
     if (host_out) HIPCHK(hipMemcpyAsync(out, dev_out, n * 4, hipMemcpyDeviceToHost, st));
+    // the flags and the span count for collect(), before the slot's next group stage clears them
+    HIPCHK(hipMemcpyAsync(e->h_mirror + (size_t)G.set * MIRROR_WORDS, e->d_bsmall, MIRROR_WORDS * 4, hipMemcpyDeviceToHost,
+                          st));
     HIPCHK(hipEventRecord(B.ev[4], st));
-    B.pending = true;
-    e->last = k;
-    e->cur = k ^ 1;
-    e->gbase += n;
+    B.last_post = B.ev[4];
+    return SG_OK;
+}
+
+// Batch pipeline: the group stage of a batch runs on gstream, its decide stage on the decide streams behind the
+// previous batch's, so batch k+1's group stage overlaps batch k's decide stage.  The group stage is the longer one,
+// so the batch period is its time plus whatever gstream stands empty between two of them.  An async submit therefore
+// does not wait for its own group stage: it returns with the batch grouped, and the next submit reads that batch's
+// head (which the next group stage needs: the hot ids), queues its own first group kernel, and only then enqueues
+// the earlier batch's decide stage.  The earlier batch's verdict is that call's to return.  Buffers must stay valid
+// until sg_sync.
+static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext, uint64_t n, const sg_arg* args,
+                       uint64_t n_args, uint32_t* out) {
+    if (!e || (n && (!ev || !out))) return fail(SG_EINVAL, "null argument");
+    if (n_args && !args) return fail(SG_EINVAL, "null args table");
+    if (!e->fatal.empty()) return fail(SG_ESTATE, e->fatal + " -- engine unusable, recreate it");
+    if (n == 0) return SG_OK;
+    if (n > e->cfg.max_batch_events || n >= (1ull << 31)) return fail(SG_EINVAL, "batch larger than max_batch_events");
+    HIPCHK(hipSetDevice(e->device));
+    if (e->held_rc) return drain(e);  // an error a diagnostics export met: returned here, and this batch is not taken
+    // SG_PIPELINE=0 and SG_HANDOFF=0 hand every batch off inside its own call; so does a finite chain cap, whose
+    // grants the host orders inside the decide stage (two synchronizes, which would stall the group stage between its
+    // first kernel and the rest)
+    const bool late = e->handoff_late && e->pipeline && e->cfg.max_slot_chain_size <= 0;
+    int rc;
+    if (n > e->cap_n && (rc = drain(e))) return rc;  // (the buffers grow: no batch may be in them)
+    // what can fail without a device error comes before the grouped batch is accepted, so such a failure leaves it
+    // grouped for the next call
+    if ((rc = ensure_batch(e, n))) return rc;
+    if ((rc = ensure_pool2(e))) return rc;
+    // 1. the grouped batch's verdict: an error is this call's to return, and this batch is then not taken
+    int prev = e->grouped;
+    if (prev >= 0 && (rc = accept_grouped(e))) return rc;
+    // From here batch `prev` is counted.  Whatever makes this call fail before that batch's decide stage is enqueued
+    // enqueues it first: an accepted batch is always decided.
+    auto give_up = [&](int why) -> int {
+        if (prev >= 0) {
+            const std::string msg = g_err;
+            const int pk = prev;
+            prev = -1;
+            if (decide_stage(e, pk) == SG_OK) g_err = msg;
+        }
+        return why;
+    };
+    // the param map pool: the regions maps grew out of are dropped by a compaction between batches once the growth
+    // since the last one took half of what was free (the counts are a batch or two old); a batch that finds the pool
+    // short before that compacts on the device itself (launch_pm_grow)
+    const unsigned long long pfloor = e->h_pool_next ? e->h_pool_next[PC_FLOOR] : 0;
+    const bool compact = e->pool_nb && e->h_pool_next[PC_NEXT] > pfloor + (e->pool_nb - pfloor) / 2;
+    if (!late || compact) {  // the earlier order: the batch two back is collected before its slot is taken again
+        if (prev >= 0) {
+            const int pk = prev;
+            prev = -1;
+            if ((rc = decide_stage(e, pk))) return rc;
+        }
+        while (e->inflight.size() > 1)
+            if ((rc = collect(e))) return rc;
+    }
+    if (compact) {
+        if (int drc = drain(e)) return drc;
+        if (int crc = compact_pmaps(e)) return crc;
+        ++e->n_compact;
+    }
+    // 2.-5. the slot is reused in device order; this batch's first group kernel, the previous batch's decide stage
+    // (group_stage clears prev once it has enqueued it), the rest of this group stage
+    const int k = e->cur;
+    if ((rc = group_stage(e, k, ev, ext, n, args, n_args, out, &prev))) return give_up(rc);
+    if (!late) return handoff(e);
+    // 6. the batch before the previous one: its times and flags.  The host may wait here: nothing on the device waits
+    // for the host any more.  An error drops the batch just grouped, so a call that fails has taken no batch.
+    while (e->inflight.size() > 1)
+        if ((rc = collect(e))) {
+            (void)accept_grouped(e, true);
+            return rc;
+        }
     return SG_OK;
 }
 

@@ -1288,6 +1288,23 @@ hipError_t launch_cold_n(uint64_t n, const uint32_t* hot_total, uint32_t* out, h
 }
 uint32_t hot_max() { return HOT_MAX; }
 
+// The group stage's clears in one launch (they were three fills, each a dispatch of its own at the head of a serial
+// chain): the batch's small words, and for the hot / cold stage bst[] and the side-table marks (0 words: not cleared).
+__global__ void k_grp_clear(uint32_t* __restrict__ bsmall, uint32_t nsmall, uint32_t* __restrict__ bst, uint32_t nbst,
+                            uint32_t* __restrict__ need, uint32_t nneed) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nsmall) bsmall[i] = 0;
+    if (i < nbst) bst[i] = 0;
+    if (i < nneed) need[i] = 0;
+}
+hipError_t launch_grp_clear(uint32_t* bsmall, uint32_t nsmall, uint32_t* bst, uint32_t nbst, uint32_t* need,
+                            uint32_t nneed, hipStream_t st) {
+    uint32_t m = nsmall > nbst ? nsmall : nbst;
+    if (nneed > m) m = nneed;
+    hipLaunchKernelGGL(k_grp_clear, dim3((m + 255) / 256), dim3(256), 0, st, bsmall, nsmall, bst, nbst, need, nneed);
+    return hipGetLastError();
+}
+
 // A batch of one tile (n <= RS_TILE, the drop-in's synchronous calls): its cold (key, index) pairs -- compacted at
 // the tile's start by k_grp_first, *cnt of them -- sorted in one workgroup instead of the radix passes' ~14 launches.
 // A bitonic sort of (key << 32 | input position) is the stable sort by key the passes make; the outputs are the last

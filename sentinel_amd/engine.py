@@ -273,6 +273,18 @@ class Engine:
         k = fn(self.h, buf, cap)
         return np.frombuffer(buf, dtype=np.float64, count=4 * k).reshape(k, 4).copy()
 
+    def gap_log(self, cap: int = 4096) -> np.ndarray:
+        """How long each stream stood empty before every batch decided since the last call, [n, 2] ms: the group
+        stream from the previous batch's group end to this batch's group start, the decide stream from the previous
+        batch's post end to this batch's decide start (0, 0 for the engine's first batch); diagnostics export
+        sgx_gap_log, drains the pipeline first."""
+        buf = (C.c_double * (2 * cap))()
+        fn = lib().sgx_gap_log
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        k = fn(self.h, buf, cap)
+        return np.frombuffer(buf, dtype=np.float64, count=2 * k).reshape(k, 2).copy()
+
     def spans_total(self) -> int:
         """Frozen span slots the cooperative kernels recorded so far (diagnostics export sgx_spans_total)."""
         fn = lib().sgx_spans_total
