@@ -458,6 +458,24 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
 int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs, uint64_t n, const uint64_t* values,
                                     uint64_t n_values, sg_token_result* out);
 
+/* The value table behind sg_cluster_request_param_tokens: one slot per (flowId, value) with a count and a window
+ * stamp per bucket.  The reference clears a bucket's value map on every window reset
+ * (csrv/flow/statistic/metric/ClusterParameterLeapArray.java:30-58), so ClusterParamMetric.getSum
+ * (ClusterParamMetric.java:53-85) sees the values of the last windowIntervalMs only; here a slot is dead, and is
+ * dropped by the next rehash or rule load, once none of its stamps equals its flow's stamp of the same bucket
+ * (stamps only move forward and a count is read only under an equal stamp, so a dead slot adds 0 to every sum).
+ * The table starts at 2^SG_PV_LOG2 slots (default 17) and is rehashed on the device, before a call's first
+ * kernel, whenever the slots claimed so far plus the values the call lists would pass half of it: into the
+ * smallest power of two that leaves at most a quarter claimed, up to 2^SG_PV_MAX_LOG2 slots (default 24: 4.5 GB of
+ * 272-byte slots; the move needs the old and the new table at once, and a rehash that kept the capacity keeps the
+ * old table as the next one's target).  A call that cannot fit half of the maximum
+ * returns SG_ENOMEM before anything changed: the limiter, the flows' windows and the table are as they were.
+ * sg_cluster_param_table_stats writes up to cap values and returns how many (as sg_param_keys_stats does):
+ * [0] capacity in slots, [1] upper bound on the claimed slots (exact after a rehash or a rule load, plus the values
+ * listed since), [2] live slots kept by the last rehash, [3] rehashes, [4] rehashes that changed the capacity,
+ * [5] device time of the last rehash in microseconds (count and move, HIP events), [6] maximum capacity. */
+int sg_cluster_param_table_stats(sg_engine* e, uint64_t* out, int cap);
+
 /* Namespaces of the token server (csrv/flow/statistic/limit/GlobalRequestLimiter.java:30-80,
  * csrv/flow/rule/ClusterFlowRuleManager.java:308-317): every namespace has a RequestLimiter of its own and a
  * connected-client count of its own, and a token request tries the limiter of its flowId's namespace only

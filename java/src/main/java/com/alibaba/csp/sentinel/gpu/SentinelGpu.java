@@ -231,6 +231,10 @@ final class SentinelGpu {
         rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));
     static final MethodHandle CLUSTER_REQUEST_PARAM_TOKENS = fn("sg_cluster_request_param_tokens",
         rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS));
+    /** The param value table: (engine, long* out, cap) -> values written (capacity, claimed bound, live kept,
+     *  rehashes, resizes, last rehash in us, maximum capacity). */
+    static final MethodHandle CLUSTER_PARAM_TABLE_STATS = fn("sg_cluster_param_table_stats",
+        rc(ADDRESS, ADDRESS, JAVA_INT));
     /** Namespaces: (engine, ns, maxAllowedQps, int* id) / (engine, ns, long* flowIds, n) / (engine, ns, connected) /
      *  (engine, ns, now, double* currentQps, double* maxAllowedQps). */
     static final MethodHandle CLUSTER_NAMESPACE = fn("sg_cluster_namespace",

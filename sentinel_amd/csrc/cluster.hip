@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "chain.h"
+#include "pvtab.h"
 
 namespace sg {
 
@@ -741,7 +742,7 @@ __device__ __forceinline__ int pf_current(PFlow& F, int64_t now) {  // LeapArray
 }
 __device__ PVal* pv_find(PVal* __restrict__ tab, uint32_t mask, uint32_t f, uint64_t key, bool create,
                          uint32_t* __restrict__ flags) {
-    uint64_t h = tab_hash((int64_t)(key ^ ((uint64_t)f * 0xD6E8FEB86659FD93ull))) & mask;
+    uint64_t h = pv_hash(f, key) & mask;
     for (uint32_t probe = 0; probe <= mask; ++probe) {
         PVal* s = &tab[h];
         uint32_t owner = __hip_atomic_load(&s->flow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -757,7 +758,7 @@ __device__ PVal* pv_find(PVal* __restrict__ tab, uint32_t mask, uint32_t f, uint
         if (owner == f && s->key == key) return s;
         h = (h + 1) & mask;
     }
-    atomicOr(flags, 2u);  // table full
+    atomicOr(flags, 2u);  // table full (a backstop: the host makes room before the launch, pvtab.h)
     return nullptr;
 }
 __global__ void k_ptok_flow(const uint32_t* __restrict__ skeys, const uint32_t* __restrict__ svals, uint64_t n,
@@ -824,6 +825,67 @@ hipError_t launch_ptok_flow(const uint32_t* skeys, const uint32_t* svals, uint64
     if (!n || !nflows) return hipSuccess;
     hipLaunchKernelGGL(k_ptok_flow, dim3((nflows + 255) / 256), dim3(256), 0, st, skeys, svals, n, req, values, flows,
                        nflows, hot, tab, mask, res, flags);
+    return hipGetLastError();
+}
+
+// ---- the value table's rehash (pvtab.h): count the live slots, or move them into a second table.
+// A grid-stride pass over the old slots, one lane a slot.  A slot is live by pv_live against its flow's current
+// window stamps; dst == nullptr only counts.  A live slot CAS-claims `flow` in dst by the linear probe of pv_find
+// (dst starts all PV_EMPTY, and (flow, key) is unique in the old table, so a claim never meets its own pair) and
+// is then copied whole as 17 uint4 (272 B; key, every ws[j] and every cnt[j] unchanged).  out[0] += slots counted
+// or moved (one atomic a wave), out[1] |= 1 when dst had no free slot (the host sized it: unreachable).
+// Nothing else touches either table meanwhile: the host runs this on the engine stream after drain.
+static_assert(sizeof(PVal) == 272 && sizeof(PVal) % sizeof(uint4) == 0, "k_pv_rehash copies a slot as 17 uint4");
+__global__ __launch_bounds__(256) void k_pv_rehash(const PVal* __restrict__ src, uint64_t n_src,
+                                                   const PFlow* __restrict__ flows, uint32_t nflows,
+                                                   PVal* __restrict__ dst, uint32_t dmask,
+                                                   uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n_src; base += stride) {  // (uniform in a wave)
+        const uint64_t i = base + threadIdx.x;
+        bool live = false;
+        if (i < n_src) {
+            const uint32_t f = src[i].flow;
+            if (f != PV_EMPTY && f < nflows) {
+                const PFlow* F = &flows[f];
+                const int fn = F->n < CP_MAXN ? F->n : CP_MAXN;
+                for (int j = 0; j < fn; ++j) {  // pv_live, without a private copy of the flow
+                    const int64_t w = F->fws[j];
+                    if (w >= 0 && src[i].ws[j] == w) { live = true; break; }
+                }
+                if (live && dst) {
+                    uint64_t h = pv_hash(f, src[i].key) & dmask;
+                    bool placed = false;
+                    for (uint32_t probe = 0; probe <= dmask; ++probe) {
+                        if (atomicCAS(&dst[h].flow, PV_EMPTY, f) == PV_EMPTY) { placed = true; break; }
+                        h = (h + 1) & dmask;
+                    }
+                    if (placed) {
+                        const uint4* s4 = reinterpret_cast<const uint4*>(&src[i]);
+                        uint4* d4 = reinterpret_cast<uint4*>(&dst[h]);
+#pragma unroll
+                        for (int k = 0; k < (int)(sizeof(PVal) / sizeof(uint4)); ++k) d4[k] = s4[k];
+                    } else {
+                        atomicOr(&out[1], 1u);
+                        live = false;
+                    }
+                }
+            }
+        }
+        const uint64_t b = __ballot(live);
+        if (b && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)b) - 1)) atomicAdd(&out[0], (uint32_t)__popcll(b));
+    }
+}
+
+// dst == nullptr: count only.  out: two words, zeroed here.
+hipError_t launch_pv_rehash(const PVal* src, uint64_t n_src, const PFlow* flows, uint32_t nflows, PVal* dst,
+                            uint32_t dmask, uint32_t* out, hipStream_t st) {
+    hipError_t rc = hipMemsetAsync(out, 0, 8, st);
+    if (rc != hipSuccess) return rc;
+    if (!n_src || !nflows) return hipSuccess;
+    const uint64_t wg = (n_src + 255) / 256;
+    hipLaunchKernelGGL(k_pv_rehash, dim3((uint32_t)(wg > 8192 ? 8192 : wg)), dim3(256), 0, st, src, n_src, flows,
+                       nflows, dst, dmask, out);
     return hipGetLastError();
 }
 

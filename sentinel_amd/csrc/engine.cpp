@@ -26,6 +26,7 @@
 #include "dev_types.h"
 #include "pkeys.h"
 #include "pmap.h"  // (pm_buckets: sg_param_thread_count)
+#include "pvtab.h"
 
 namespace sg {
 // kernels.hip
@@ -196,6 +197,8 @@ hipError_t launch_tok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_
 hipError_t launch_ptok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
                             const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
                             uint32_t mask, sg_token_result* res, uint32_t* flags, hipStream_t st);
+hipError_t launch_pv_rehash(const PVal* src, uint64_t n_src, const PFlow* flows, uint32_t nflows, PVal* dst,
+                            uint32_t dmask, uint32_t* out, hipStream_t st);
 // keysweep.hip
 hipError_t launch_keysweep(const PMap* pmap, uint32_t nm, const PBucket* pbkt, uint64_t pool_nb, const uint64_t* pbm,
                            uint64_t bm_words, const uint64_t* key_ring, uint64_t ring_n, const PVal* pvtab,
@@ -751,8 +754,15 @@ struct sg_engine {
     PHot* d_phot = nullptr;
     CSlot* d_pftab = nullptr;
     uint32_t pftab_mask = 0;
-    PVal* d_pvtab = nullptr;                      // (flow, value) counts, 2^PV_LOG2 slots
+    PVal* d_pvtab = nullptr;                      // (flow, value) counts, pv_mask + 1 slots (pvtab.h)
     uint32_t pv_mask = 0;
+    uint32_t pv_log2 = 17, pv_max_log2 = 24;      // SG_PV_LOG2, SG_PV_MAX_LOG2: initial and maximum capacity
+    uint64_t pv_claimed = 0;                      // claimed_ub: exact after a rehash or a rule load + values listed since
+    uint64_t pv_live = 0, pv_rehashes = 0, pv_resizes = 0, pv_last_us = 0;  // (sg_cluster_param_table_stats)
+    uint32_t* d_pvcnt = nullptr;                  // the rehash's two result words
+    PVal* d_pvspare = nullptr;                    // the table the last same-size rehash left: the next one's target
+    uint64_t pv_spare_cap = 0;
+    hipEvent_t pv_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     sg_param_token_req* d_preq = nullptr;
     uint64_t* d_pvals = nullptr;
     uint64_t pcap = 0, pvcap = 0;
@@ -1426,6 +1436,10 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (const char* v = std::getenv("SG_TOK_WIDE")) e->tok_wide = std::atoi(v) == 512 ? 512u : 1024u;
     if (const char* v = std::getenv("SG_TOK_LIGHT")) e->tok_light = (uint32_t)std::strtoul(v, nullptr, 0);
     if (const char* v = std::getenv("SG_TOK_NS")) e->tok_ns = v[0] == '1';
+    // the param value table's capacities (pvtab.h): 2^4 .. 2^24 slots at first, up to 2^26 (18 GB of slots)
+    if (const char* v = std::getenv("SG_PV_LOG2")) e->pv_log2 = (uint32_t)std::min(24l, std::max(4l, std::strtol(v, nullptr, 0)));
+    if (const char* v = std::getenv("SG_PV_MAX_LOG2")) e->pv_max_log2 = (uint32_t)std::min(26l, std::max(4l, std::strtol(v, nullptr, 0)));
+    e->pv_max_log2 = std::max(e->pv_max_log2, e->pv_log2);
     // ServerConstants.DEFAULT_NAMESPACE: the limiter every flowId tries until it is assigned elsewhere
     e->ns_names.push_back("default");
     e->ns_of["default"] = 0;
@@ -1596,6 +1610,8 @@ int sg_engine_destroy(sg_engine* e) {
     dfree(e->d_snap_cnt); dfree(e->d_snap_off); dfree(e->d_snap_out); dfree(e->d_dbg);
     dfree(e->d_ks_key); dfree(e->d_ks_idx); dfree(e->d_ks_marks);
     for (auto& v : e->ks_ev) if (v) (void)hipEventDestroy(v);
+    dfree(e->d_pvcnt); dfree(e->d_pvspare);
+    for (auto& v : e->pv_ev) if (v) (void)hipEventDestroy(v);
     for (auto& s : e->evset)
         for (auto& v : s) if (v) (void)hipEventDestroy(v);
     for (auto& B : e->slot) if (B.h_head) (void)hipHostFree(B.h_head);
@@ -1734,6 +1750,14 @@ int sg_param_keys_stats(sg_engine* e, uint64_t* out, int cap) {
                            e->ks_last[3]};
     int k = 0;
     for (; k < cap && k < 8; ++k) out[k] = v[k];
+    return k;
+}
+int sg_cluster_param_table_stats(sg_engine* e, uint64_t* out, int cap) {
+    if (!e || !out) return 0;
+    const uint64_t v[7] = {e->d_pvtab ? (uint64_t)e->pv_mask + 1 : 0, e->pv_claimed, e->pv_live, e->pv_rehashes,
+                           e->pv_resizes, e->pv_last_us, 1ull << e->pv_max_log2};
+    int k = 0;
+    for (; k < cap && k < 7; ++k) out[k] = v[k];
     return k;
 }
 // diagnostics export: the last sweep's scans in ms {maps, key ring, token server values}
@@ -2024,8 +2048,8 @@ int sg_load_degrade_rules(sg_engine* e, const sg_degrade_rule* rules, uint32_t n
 // ClusterParamFlowRuleManager.applyClusterParamRules (csrv/flow/rule/ClusterParamFlowRuleManager.java:318-369):
 // cluster-mode rules passing ParamFlowRuleUtil.isValidRule, in list order; the last rule of a flowId wins;
 // putMetricIfAbsent keeps the metric (window shape and value counts) of a flowId that stays; the metrics of
-// the others are dropped (their value slots leave the table).
-#define PV_LOG2 17
+// the others are dropped (their value slots leave the table, and so do the dead slots of the flows that stay:
+// pvtab.h).  The table keeps its capacity.
 static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const std::vector<ParamR>& all, uint32_t n) {
     std::vector<int64_t> order;
     std::unordered_map<int64_t, uint32_t> rule_of;
@@ -2068,19 +2092,23 @@ static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const
         nmap[fid] = (uint32_t)nf.size();
         nf.push_back(f);
     }
-    const uint32_t cap_v = 1u << PV_LOG2;
+    const uint32_t cap_v = e->d_pvtab ? e->pv_mask + 1 : 1u << e->pv_log2;
     const bool need_v = !nf.empty() || e->d_pvtab;  // no table until a cluster param rule exists
     std::vector<PVal> vt(need_v ? cap_v : 0);
     if (!need_v) {}
     else if (e->d_pvtab) HIPCHK(hipMemcpy(vt.data(), e->d_pvtab, cap_v * sizeof(PVal), hipMemcpyDeviceToHost));
     else for (auto& v : vt) v.flow = PV_EMPTY;
-    // re-insert the value slots of the flows that stay, under their new flow index (same probe as pv_find)
+    // re-insert the live value slots of the flows that stay, under their new flow index (same probe as pv_find)
     std::vector<PVal> keep;
-    for (auto& v : vt) if (v.flow != PV_EMPTY && v.flow < nold && remap[v.flow] != PV_EMPTY) { keep.push_back(v); keep.back().flow = remap[v.flow]; }
+    for (auto& v : vt)
+        if (v.flow != PV_EMPTY && v.flow < nold && remap[v.flow] != PV_EMPTY && pv_live(old_f[v.flow], v)) {
+            keep.push_back(v);
+            keep.back().flow = remap[v.flow];
+        }
     for (auto& v : vt) { v.flow = PV_EMPTY; v.key = 0; }
-    for (auto& v : keep) {
-        uint64_t h = tab_hash_h((int64_t)(v.key ^ ((uint64_t)v.flow * 0xD6E8FEB86659FD93ull))) & (cap_v - 1);
-        while (vt[h].flow != PV_EMPTY) h = (h + 1) & (cap_v - 1);
+    for (auto& v : keep) {  // (at most half of cap_v: there is a free slot)
+        const uint64_t h = pv_probe(vt.data(), cap_v, v.flow, v.key);
+        if (h >= cap_v) return fail(SG_ECAPACITY, "cluster param value table is full");
         vt[h] = v;
     }
     uint32_t cap = 16;
@@ -2108,6 +2136,7 @@ static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const
         if (!e->d_pvtab) HIPCHK(hipMalloc(&e->d_pvtab, cap_v * sizeof(PVal)));
         HIPCHK(hipMemcpy(e->d_pvtab, vt.data(), cap_v * sizeof(PVal), hipMemcpyHostToDevice));
         e->pv_mask = cap_v - 1;
+        e->pv_claimed = keep.size();
     }
     HIPCHK(hipMalloc(&e->d_pftab, cap * sizeof(CSlot)));
     HIPCHK(hipMemcpy(e->d_pftab, tab.data(), cap * sizeof(CSlot), hipMemcpyHostToDevice));
@@ -3760,6 +3789,70 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
     return SG_OK;
 }
 
+// Room in the value table for a call of V listed values, before any kernel of the call runs (pvtab.h; in the
+// spirit of k_pm_grow).  While claimed_ub + V fits half the table this is one comparison.  Otherwise the live
+// slots are counted on the device, pv_plan picks the capacity, and k_pv_rehash moves them into a fresh table
+// (a rehash that keeps the capacity keeps the old table as the next one's target, so a steady stream allocates
+// nothing; a resize frees it; either way two tables exist during the move).  A refusal (SG_ENOMEM: the maximum
+// capacity cannot hold the live values and V at half load, or the second table cannot be allocated) leaves the
+// table, the limiter and the flows' windows as they were.  Runs on the engine stream after drain.
+static int pv_make_room(sg_engine* e, uint64_t V) {
+    if (!e->d_pvtab || e->pflows.empty()) return SG_OK;
+    const uint64_t cap = (uint64_t)e->pv_mask + 1;
+    if (pv_has_room(e->pv_claimed, V, cap)) return SG_OK;
+    hipStream_t st = e->stream;
+    const uint32_t nflows = (uint32_t)e->pflows.size();
+    if (!e->d_pvcnt) HIPCHK(hipMalloc(&e->d_pvcnt, 8));
+    for (auto& v : e->pv_ev)
+        if (!v) HIPCHK(hipEventCreate(&v));
+    uint32_t cnt[2] = {0, 0};
+    HIPCHK(hipEventRecord(e->pv_ev[0], st));
+    HIPCHK(launch_pv_rehash(e->d_pvtab, cap, e->d_pflow, nflows, nullptr, 0, e->d_pvcnt, st));
+    HIPCHK(hipEventRecord(e->pv_ev[1], st));
+    HIPCHK(hipMemcpyAsync(cnt, e->d_pvcnt, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t live = cnt[0];
+    const uint64_t ncap = pv_plan(live, V, 1ull << e->pv_log2, 1ull << e->pv_max_log2);
+    if (!ncap)
+        return fail(SG_ENOMEM, "cluster param value table: the live values and this call's do not fit half of the "
+                               "maximum capacity (SG_PV_MAX_LOG2)");
+    PVal* nt = nullptr;
+    if (e->d_pvspare && e->pv_spare_cap == ncap) {
+        nt = e->d_pvspare;
+        e->d_pvspare = nullptr;
+    } else {
+        dfree(e->d_pvspare);
+        if (hipMalloc(&nt, ncap * sizeof(PVal)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SG_ENOMEM, "cluster param value table: no device memory for the larger table");
+        }
+    }
+    hipError_t rc = hipEventRecord(e->pv_ev[2], st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(nt, 0xFF, ncap * sizeof(PVal), st);  // every flow PV_EMPTY
+    if (rc == hipSuccess) rc = launch_pv_rehash(e->d_pvtab, cap, e->d_pflow, nflows, nt, (uint32_t)(ncap - 1), e->d_pvcnt, st);
+    if (rc == hipSuccess) rc = hipEventRecord(e->pv_ev[3], st);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(cnt, e->d_pvcnt, 8, hipMemcpyDeviceToHost, st);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+    if (rc != hipSuccess || cnt[1] || cnt[0] != live) {  // (the old table is untouched: it stays)
+        (void)hipFree(nt);
+        if (rc != hipSuccess) return fail(SG_EDEVICE, std::string("cluster param value table rehash: ") + hipGetErrorString(rc));
+        return fail(SG_EDEVICE, "cluster param value table rehash lost a slot");
+    }
+    float ms0 = 0, ms1 = 0;
+    if (hipEventElapsedTime(&ms0, e->pv_ev[0], e->pv_ev[1]) != hipSuccess) ms0 = 0;
+    if (hipEventElapsedTime(&ms1, e->pv_ev[2], e->pv_ev[3]) != hipSuccess) ms1 = 0;
+    (void)hipGetLastError();
+    if (ncap == cap) { e->d_pvspare = e->d_pvtab; e->pv_spare_cap = cap; }
+    else (void)hipFree(e->d_pvtab);
+    e->d_pvtab = nt;
+    e->pv_mask = (uint32_t)(ncap - 1);
+    e->pv_claimed = e->pv_live = live;
+    e->pv_last_us = (uint64_t)(((double)ms0 + (double)ms1) * 1000.0);
+    ++e->pv_rehashes;
+    if (ncap != cap) ++e->pv_resizes;
+    return SG_OK;
+}
+
 // Batched DefaultTokenService.requestParamToken: the flow path's classify and namespace limiter steps on a
 // derived sg_token_req view (n_values == 0 -> acquire 0 -> BAD_REQUEST), then k_ptok_flow per param flow.
 int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs, uint64_t n, const uint64_t* values,
@@ -3767,10 +3860,14 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
     if (!e || (n && (!reqs || !out)) || (n_values && !values)) return fail(SG_EINVAL, "null argument");
     if (!n) return SG_OK;
     if (n > 0x7FFFFFFFull) return fail(SG_EINVAL, "too many token requests in one call");
-    for (uint64_t i = 0; i < n; ++i)
+    uint64_t listed = 0;  // values the requests list: the call claims at most that many value slots
+    for (uint64_t i = 0; i < n; ++i) {
         if (reqs[i].value_off > n_values || reqs[i].n_values > n_values - reqs[i].value_off)
             return fail(SG_EINVAL, "param token request values out of range");
+        listed += reqs[i].n_values;
+    }
     if (int rc = drain(e)) return rc;
+    if (int rc = pv_make_room(e, listed)) return rc;  // before the limiter or any window moves
     hipStream_t st = e->stream;
     int rc = ensure_batch(e, n);
     if (rc) return rc;
@@ -3839,6 +3936,7 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
             std::swap(kin, kout);
             std::swap(vin, vout);
         }
+        e->pv_claimed += listed;
         HIPCHK(launch_ptok_flow(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab,
                                 e->pv_mask, e->d_tres, e->d_small, st));
     }

@@ -27,7 +27,7 @@ EXPORTS = (
     "sg_submit_ex", "sg_submit_ex_async", "sg_intern_origin", "sg_intern_context", "sg_param_thread_count",
     "sg_cluster_namespace", "sg_cluster_assign_flows", "sg_cluster_set_namespace_connected",
     "sg_cluster_namespace_qps", "sg_load_authority_rules", "sg_param_intern", "sg_param_intern_batch",
-    "sg_param_keys_sweep", "sg_param_keys_stats",
+    "sg_param_keys_sweep", "sg_param_keys_stats", "sg_cluster_param_table_stats",
 )
 
 
@@ -70,6 +70,7 @@ def lib():
         L.sg_cluster_set_connected_count.argtypes = [P, C.c_int64, C.c_int32]
         L.sg_cluster_request_tokens.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p]
         L.sg_cluster_request_param_tokens.argtypes = [P, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.sg_cluster_param_table_stats.argtypes = [P, C.POINTER(C.c_uint64), C.c_int]
         L.sg_cluster_namespace.argtypes = [P, C.c_char_p, C.c_double, C.POINTER(C.c_uint32)]
         L.sg_cluster_assign_flows.argtypes = [P, C.c_char_p, C.POINTER(C.c_int64), C.c_uint32]
         L.sg_cluster_set_namespace_connected.argtypes = [P, C.c_char_p, C.c_int32]
@@ -439,3 +440,12 @@ class Engine:
         arr, vals = A.param_token_arrays(reqs)
         out = self.cluster_request_param_array(arr, vals)
         return [(int(o["status"]), int(o["remaining"]), int(o["wait_in_ms"])) for o in out]
+
+    def cluster_param_table_stats(self) -> dict:
+        """sg_cluster_param_table_stats: the (flowId, value) table behind cluster_request_param.  It drops the
+        values no window holds any more and grows from 2^SG_PV_LOG2 up to 2^SG_PV_MAX_LOG2 slots; a call that
+        cannot fit raises SentinelError(SG_ENOMEM) with nothing changed."""
+        out = (C.c_uint64 * 7)()
+        k = lib().sg_cluster_param_table_stats(self.h, out, 7)
+        names = ("capacity", "claimed_ub", "live_kept", "rehashes", "resizes", "rehash_us", "max_capacity")
+        return {names[i]: int(out[i]) for i in range(k)}

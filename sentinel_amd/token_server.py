@@ -308,6 +308,12 @@ class TokenServer:
             except asyncio.CancelledError:
                 pass
 
+    def param_table_stats(self) -> dict:
+        """The service's `cluster_param_table_stats()` (the PARAM_FLOW value table: capacity, claimed bound,
+        rehashes ...; observability, next to `sweeps`); {} for a service without it."""
+        fn = getattr(self.service, "cluster_param_table_stats", None)
+        return fn() if fn is not None else {}
+
     def _update_connected(self, namespace: str):
         n = self.conns.count(namespace)
         if self.ns_qps is not None and namespace in self.ns_qps:
