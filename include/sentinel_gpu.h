@@ -343,7 +343,10 @@ int sg_resource_id(sg_engine* e, const char* name, uint32_t* out_id);
  * Loading a list equal to the current one is a no-op (DynamicSentinelProperty
  * .updateValue, core/property/DynamicSentinelProperty.java:49-52); any other
  * list replaces the rules with fresh controller/breaker state.  *n_loaded
- * (optional) receives the number of valid rules kept. */
+ * (optional) receives the number of valid rules kept.  A load that is refused
+ * for its size (SG_ENOTSUP: a 17th rule on one resource, SG_ECAPACITY: more
+ * than cfg.max_rules) leaves the engine as it was, but for the resource names
+ * it registered: the old rules of every kind go on deciding on their state. */
 int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint32_t* n_loaded);
 int sg_load_degrade_rules(sg_engine* e, const sg_degrade_rule* rules, uint32_t n, uint32_t* n_loaded);
 int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, uint32_t* n_loaded);

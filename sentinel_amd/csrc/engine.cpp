@@ -1297,6 +1297,35 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
     return SG_OK;
 }
 
+// What upload_rules refuses for its size -- more than 16 compiled rules on one resource, more than max_rules in all --
+// told from the host lists alone.  The loaders call it with the lists they are about to publish, before they change
+// anything of the engine: a load refused for its size leaves the engine as it was.
+static int check_rule_limits(const sg_engine* e, const std::vector<ParamR>& params, const std::vector<std::vector<int>>& res_par,
+                             const std::vector<FlowR>& flows, const std::vector<std::vector<int>>& res_flow,
+                             const std::vector<std::vector<int>>& res_deg) {
+    size_t total = 0;
+    const size_t nres = std::min<size_t>(e->names.size(), e->cfg.max_resources);
+    for (size_t r = 0; r < nres; ++r) {
+        size_t n = r < res_deg.size() ? res_deg[r].size() : 0;
+        bool run = false;  // the last compiled param rule is a PB_INIT_ONLY pseudo-rule with a fixed index
+        if (r < res_par.size())
+            for (int i : res_par[r]) {
+                const sg_param_rule& q = params[i].r;
+                const bool init = q.cluster_mode && q.grade == SG_FLOW_GRADE_QPS && !q.cluster_fallback_to_local;
+                if (init && q.param_idx >= 0 && run) continue;  // joins the pseudo-rule before it
+                run = init && q.param_idx >= 0;
+                ++n;
+            }
+        if (r < res_flow.size())
+            for (int i : res_flow[r])
+                if (!(flows[i].r.cluster_mode && !flows[i].r.cluster_fallback_to_local)) ++n;
+        if (n > 16) return fail(SG_ENOTSUP, "more than 16 rules on one resource: " + e->names[r]);
+        total += n;
+    }
+    if (total > e->cfg.max_rules) return fail(SG_ECAPACITY, "compiled rule table exceeds max_rules");
+    return SG_OK;
+}
+
 uint32_t intern(sg_engine* e, const std::string& name) {
     auto it = e->ids.find(name);
     if (it != e->ids.end()) return it->second;
@@ -1909,9 +1938,11 @@ int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint
             return cmp(x, y) < 0;
         });
     }
+    if (int rc = check_rule_limits(e, e->params, e->res_par, flows, per, e->res_deg)) return rc;
     // publish
     auto old_flows = std::move(e->flows);
     auto old_per = std::move(e->res_flow);
+    auto old_names = std::move(e->rule_names);
     e->flows = std::move(flows);
     e->res_flow = std::move(per);
     resize_lists(e, e->res_flow);
@@ -1921,7 +1952,12 @@ int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint
         if (f.r.strategy == SG_STRATEGY_CHAIN) e->rule_names["c\x01" + f.ref] = 1;
     }
     int rc = upload_rules(e, true, false, false);
-    if (rc) { e->flows = std::move(old_flows); e->res_flow = std::move(old_per); return rc; }
+    if (rc) {  // the old rules go on deciding: their names too (an origin of theirs interned later recompiles them)
+        e->flows = std::move(old_flows);
+        e->res_flow = std::move(old_per);
+        e->rule_names = std::move(old_names);
+        return rc;
+    }
     e->last_flow = keys;
     e->flow_loaded = true;
     rc = rebuild_cluster(e, rules, n);
@@ -2031,6 +2067,7 @@ int sg_load_degrade_rules(sg_engine* e, const sg_degrade_rule* rules, uint32_t n
     std::vector<int32_t> hs(degs.size());
     for (size_t i = 0; i < degs.size(); ++i) hs[i] = degs[i].hash;
     for (auto& l : per) hashset_order(hs, l);
+    if (int rc = check_rule_limits(e, e->params, e->res_par, e->flows, e->res_flow, per)) return rc;
     auto od = std::move(e->degs);
     auto op = std::move(e->res_deg);
     e->degs = std::move(degs);
@@ -2423,7 +2460,8 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
             for (int32_t k = 0; k < SG_MAX_ARGS; ++k)
                 if (idx < 0 || idx == k) tmaps.insert(((uint64_t)r << 8) | (uint64_t)k);
         }
-    // the capacity check first: with SG_ECAPACITY neither the cluster rules nor the maps change
+    // the checks first: with SG_ENOTSUP / SG_ECAPACITY neither the cluster rules nor the maps change
+    if (int rc = check_rule_limits(e, ps, per, e->flows, e->res_flow, e->res_deg)) return rc;
     uint64_t need = (rcap.size() + tmaps.size()) * (uint64_t)PM_MIN_NB * PM_BKT;  // (new maps' first regions)
     if (need > (1ull << e->cfg.param_table_log2))
         return fail(SG_ECAPACITY, "hot-parameter maps need " + std::to_string(need) + " slots, param_table_log2 = " +
