@@ -457,7 +457,14 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
  * Rules come from the param rules loaded with cluster_mode=1 (the ClusterParamFlowRuleManager role,
  * csrv/flow/rule/ClusterParamFlowRuleManager.java:318-369).  Request i names its parameter values
  * as values[value_off, value_off + n_values): interned 64-bit keys (sg_param_key).  Requests are
- * time-ordered and share the namespace's GlobalRequestLimiter with sg_cluster_request_tokens. */
+ * time-ordered and share the namespace's GlobalRequestLimiter with sg_cluster_request_tokens.
+ * reqs, values and out may each be host or device memory; the call returns when the results are
+ * written.  A value range outside values[0, n_values) or unordered ts returns SG_EINVAL, a call whose
+ * values cannot fit the value table SG_ENOMEM; either leaves the limiter, the windows and the table
+ * as they were.  The flow stage is decided with one lane per (flowId, value) chain across the device;
+ * for a call, a flow with a request of more than one value, or whose first request lies before one
+ * of its window starts (the clock went back between calls), is decided by one lane in request order
+ * instead (SG_PTOK_VP=0: every flow).  The decisions are the same either way. */
 int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs, uint64_t n, const uint64_t* values,
                                     uint64_t n_values, sg_token_result* out);
 
@@ -476,7 +483,10 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
  * sg_cluster_param_table_stats writes up to cap values and returns how many (as sg_param_keys_stats does):
  * [0] capacity in slots, [1] upper bound on the claimed slots (exact after a rehash or a rule load, plus the values
  * listed since), [2] live slots kept by the last rehash, [3] rehashes, [4] rehashes that changed the capacity,
- * [5] device time of the last rehash in microseconds (count and move, HIP events), [6] maximum capacity. */
+ * [5] device time of the last rehash in microseconds (count and move, HIP events), [6] maximum capacity,
+ * and, cumulative over the engine's calls (a refused call changes none): [7] flow-stage requests decided by the
+ * value-parallel owner, [8] by the one-lane-per-flow owner, [9] flows the latter kept for a call because of a
+ * multi-value request or a clock gone back. */
 int sg_cluster_param_table_stats(sg_engine* e, uint64_t* out, int cap);
 
 /* Namespaces of the token server (csrv/flow/statistic/limit/GlobalRequestLimiter.java:30-80,

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "chain.h"
+#include "ptok.h"
 #include "pvtab.h"
 
 namespace sg {
@@ -729,10 +730,12 @@ hipError_t launch_tok_limiter_par(const sg_token_req* req, uint64_t n, const uin
 }
 
 // ---- ClusterParamFlowChecker.acquireClusterToken (csrv/flow/ClusterParamFlowChecker.java:42-88)
-// One lane per param flow over its requests in time order (sorted positions).  The
+// One lane per param flow over its requests in time order (sorted positions): the owner of the flows that
+// k_ptok_elig keeps serial for the call (the value-parallel owner below takes the others).  The
 // flow's ClusterParameterLeapArray keeps per-bucket value maps; here a value's counts live in a PVal
 // slot of an open-addressing table shared by all flows (claimed by CAS on PVal.flow; a lane only ever
-// looks up its own flow's values, which it inserted itself, so a lookup never races an insert it needs).
+// looks up its own flow's values, which it inserted itself, so a lookup never races an insert it needs:
+// the value-parallel owner works on other flows, and on the same stream after this kernel).
 __device__ __forceinline__ int pf_current(PFlow& F, int64_t now) {  // LeapArray.currentWindow (create / reset)
     const int64_t wlen = F.interval / F.n;
     const int idx = (int)((now / wlen) % F.n);
@@ -765,14 +768,19 @@ __global__ void k_ptok_flow(const uint32_t* __restrict__ skeys, const uint32_t* 
                             const sg_param_token_req* __restrict__ req, const uint64_t* __restrict__ values,
                             PFlow* __restrict__ flows, uint32_t nflows, const PHot* __restrict__ hot,
                             PVal* __restrict__ tab, uint32_t mask, sg_token_result* __restrict__ res,
-                            uint32_t* __restrict__ flags) {
+                            uint32_t* __restrict__ flags, const uint32_t* __restrict__ serial,
+                            unsigned long long* __restrict__ ctr) {
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nflows) return;
+    // serial: the per-flow words of k_ptok_elig (0: the value-parallel owner's flow for this call); nullptr: every
+    // flow is this kernel's, and it counts its requests itself (ctr[1], else k_ptok_keys does)
+    if (serial && !serial[f]) return;
     uint64_t lo = 0, hi = n;
     while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (skeys[mid] < f) lo = mid + 1; else hi = mid; }
     uint64_t e = lo, h2 = n;
     while (e < h2) { const uint64_t mid = (e + h2) / 2; if (skeys[mid] <= f) e = mid + 1; else h2 = mid; }
     if (lo == e) return;
+    if (ctr) atomicAdd(&ctr[1], (unsigned long long)(e - lo));
     PFlow F = flows[f];
     const double isec = F.interval / 1000.0;  // LeapArray.getIntervalInSecond
     for (uint64_t p = lo; p < e; ++p) {
@@ -821,10 +829,267 @@ __global__ void k_ptok_flow(const uint32_t* __restrict__ skeys, const uint32_t* 
 
 hipError_t launch_ptok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
                             const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
-                            uint32_t mask, sg_token_result* res, uint32_t* flags, hipStream_t st) {
+                            uint32_t mask, sg_token_result* res, uint32_t* flags, const uint32_t* serial,
+                            unsigned long long* ctr, hipStream_t st) {
     if (!n || !nflows) return hipSuccess;
     hipLaunchKernelGGL(k_ptok_flow, dim3((nflows + 255) / 256), dim3(256), 0, st, skeys, svals, n, req, values, flows,
-                       nflows, hot, tab, mask, res, flags);
+                       nflows, hot, tab, mask, res, flags, serial, ctr);
+    return hipGetLastError();
+}
+
+// ---- the param call's request view (sg_cluster_request_param_tokens takes host or device buffers)
+// One lane a request: the sg_token_req the classify and limiter steps read (n_values == 0 -> acquire 0 ->
+// BAD_REQUEST), st[0] += the values the requests list (one atomic a wave), st[1] |= 1 when a request's
+// [value_off, value_off + n_values) leaves the values array.
+__global__ __launch_bounds__(256) void k_ptok_prep(const sg_param_token_req* __restrict__ preq, uint64_t n,
+                                                   uint64_t n_values, sg_token_req* __restrict__ treq,
+                                                   unsigned long long* __restrict__ st) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long nv = 0;
+    if (i < n) {
+        const sg_param_token_req q = preq[i];
+        if (q.value_off > n_values || q.n_values > n_values - q.value_off) atomicOr(&st[1], 1ull);
+        nv = q.n_values;
+        sg_token_req t;
+        t.ts = q.ts;
+        t.flow_id = q.flow_id;
+        t.acquire_count = q.n_values ? q.acquire_count : 0;  // empty params -> badRequest
+        t.prioritized = 0;
+        treq[i] = t;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) nv += __shfl_xor(nv, o, 64);
+    if ((threadIdx.x & 63) == 0 && nv) atomicAdd(&st[0], nv);
+}
+
+// ---- the value-parallel owner (ptok.h has the derivation and the walk)
+// After the flow sort (skeys / svals: flow index, request index; skeys == nflows: not for a flow) every flow-stage
+// request of a flow whose word of `serial` stays 0 is one access of a (flow, value) chain:
+//   k_ptok_elig    the per-flow word: PT_MULTI or PT_CLOCK (then k_ptok_flow keeps the flow);
+//   k_ptok_lookup  the access's slot by a read-only probe (nothing inserts meanwhile), and for a pair the table
+//                  does not hold one representative access: the pairs meet in the call's scratch table `dedup`,
+//                  whose words are access positions claimed by CAS -- a word, once set, names an immutable request,
+//                  so a reader compares against that request's (flow, value) and can never misread a half-written
+//                  entry, and nobody waits;
+//   k_ptok_claim   the representative alone claims the pair's slot: the first free slot of its probe (CAS on
+//                  PVal.flow, as k_pv_rehash does; slots are never freed inside a call, so the first free one
+//                  ends the pair's probe) -- it compares no key, so another claimer's unwritten key is never read;
+//   k_ptok_keys    the sort key of every position (the slot, or `sent` for what is not the owner's), the flow's
+//                  stamp merge (an atomic maximum at the last request of each window of the flow) and the
+//                  counters; then the stable radix sort by slot keeps a chain's accesses in time order;
+//   k_ptok_gather  ts and acquire of the sorted accesses, dense;
+//   k_ptok_chain   one lane per group start walks its chain with the slot's stamps and counts in registers.
+#define PT_MISS 0x80000000u  // slotof: the pair had no slot when the call began (its representative claims one)
+#define PT_NONE 0xFFFFFFFFu
+
+__global__ __launch_bounds__(256) void k_ptok_elig(const uint32_t* __restrict__ skeys, const uint32_t* __restrict__ svals,
+                                                   uint64_t n, const sg_param_token_req* __restrict__ req,
+                                                   const PFlow* __restrict__ flows, uint32_t nflows,
+                                                   uint32_t* __restrict__ serial) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t f = skeys[p];
+    if (f >= nflows) return;
+    const bool first = p == 0 || skeys[p - 1] != f;
+    uint32_t bits = 0;
+    const sg_param_token_req q = req[svals[p]];
+    if (q.n_values > 1) bits |= PT_MULTI;
+    if (first && !pt_clock_ok(flows[f], q.ts)) bits |= PT_CLOCK;
+    if (bits) atomicOr(&serial[f], bits);
+}
+
+__device__ __forceinline__ void pt_count(bool pred, unsigned long long* ctr) {  // *ctr += lanes with pred
+    const uint64_t b = __ballot(pred);
+    if (b && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)b) - 1)) atomicAdd(ctr, (unsigned long long)__popcll(b));
+}
+
+__global__ __launch_bounds__(256) void k_ptok_lookup(const uint32_t* __restrict__ skeys, const uint32_t* __restrict__ svals,
+                                                     uint64_t n, const sg_param_token_req* __restrict__ req,
+                                                     const uint64_t* __restrict__ values, uint32_t nflows,
+                                                     const uint32_t* __restrict__ serial, const PVal* __restrict__ tab,
+                                                     uint32_t mask, uint32_t* __restrict__ dedup, uint32_t dmask,
+                                                     uint32_t* __restrict__ slotof, uint32_t* __restrict__ rep) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t f = skeys[p];
+    if (f >= nflows || serial[f]) { slotof[p] = PT_NONE; return; }
+    const uint64_t key = values[req[svals[p]].value_off];
+    const uint64_t hh = pv_hash(f, key);
+    uint64_t h = hh & mask;
+    for (uint32_t probe = 0; probe <= mask; ++probe) {
+        const uint32_t owner = tab[h].flow;
+        if (owner == PV_EMPTY) break;
+        if (owner == f && tab[h].key == key) { slotof[p] = (uint32_t)h; return; }
+        h = (h + 1) & mask;
+    }
+    uint32_t d = (uint32_t)(hh >> 32) & dmask, r = (uint32_t)p;
+    for (;;) {  // (dedup has at least twice as many words as the call has requests: a free word ends the probe)
+        const uint32_t cur = atomicCAS(&dedup[d], PT_NONE, (uint32_t)p);
+        if (cur == PT_NONE) break;
+        if (skeys[cur] == f && values[req[svals[cur]].value_off] == key) { r = cur; break; }
+        d = (d + 1) & dmask;
+    }
+    slotof[p] = PT_MISS;
+    rep[p] = r;
+}
+
+__global__ __launch_bounds__(256) void k_ptok_claim(const uint32_t* __restrict__ skeys, const uint32_t* __restrict__ svals,
+                                                    uint64_t n, const sg_param_token_req* __restrict__ req,
+                                                    const uint64_t* __restrict__ values, PVal* __restrict__ tab,
+                                                    uint32_t mask, uint32_t* __restrict__ slotof,
+                                                    const uint32_t* __restrict__ rep, uint32_t* __restrict__ flags) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || slotof[p] != PT_MISS || rep[p] != (uint32_t)p) return;
+    const uint32_t f = skeys[p];
+    const uint64_t key = values[req[svals[p]].value_off];
+    uint64_t h = pv_hash(f, key) & mask;
+    for (uint32_t probe = 0; probe <= mask; ++probe) {
+        if (atomicCAS(&tab[h].flow, PV_EMPTY, f) == PV_EMPTY) {
+            PVal* s = &tab[h];
+            s->key = key;
+            for (int j = 0; j < CP_MAXN; ++j) { s->ws[j] = -1; s->cnt[j] = 0; }
+            slotof[p] = (uint32_t)h;
+            return;
+        }
+        h = (h + 1) & mask;
+    }
+    slotof[p] = PT_NONE;  // table full (a backstop: the host made room before the launch, pvtab.h)
+    atomicOr(flags, 2u);
+}
+
+// ctr: [0] requests the value-parallel owner decides, [1] requests k_ptok_flow decides, [2] flows k_ptok_flow keeps
+// because of PT_MULTI or PT_CLOCK (cumulative over the engine's calls)
+__global__ __launch_bounds__(256) void k_ptok_keys(const uint32_t* __restrict__ skeys, const uint32_t* __restrict__ svals,
+                                                   uint64_t n, const sg_param_token_req* __restrict__ req,
+                                                   PFlow* __restrict__ flows, uint32_t nflows,
+                                                   const uint32_t* __restrict__ serial, const uint32_t* __restrict__ slotof,
+                                                   const uint32_t* __restrict__ rep, uint32_t sent,
+                                                   uint32_t* __restrict__ okeys, uint32_t* __restrict__ ovals,
+                                                   sg_token_result* __restrict__ res, unsigned long long* __restrict__ ctr) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = p < n;
+    const uint32_t f = in ? skeys[p] : nflows;
+    const bool stage = in && f < nflows;
+    const uint32_t why = stage ? serial[f] : 0;
+    const bool vp = stage && !why;
+    pt_count(vp, &ctr[0]);
+    pt_count(stage && why, &ctr[1]);
+    pt_count(stage && why && (p == 0 || skeys[p - 1] != f), &ctr[2]);
+    if (!in) return;
+    const uint32_t i = svals[p];
+    uint32_t key = sent;
+    if (vp) {
+        uint32_t s = slotof[p];
+        if (s == PT_MISS) s = slotof[rep[p]];
+        if (s == PT_NONE) res[i].status = SG_TOKEN_BLOCKED;  // (table full: the call fails)
+        else key = s;
+        // the flow's stamp merge (ptok.h pt_merge): the last request of each window of the flow carries its stamp
+        const int32_t fn = flows[f].n, fi = flows[f].interval;
+        const PtWin w = pt_window(fn, fi, req[i].ts);
+        bool last = p + 1 >= n || skeys[p + 1] != f;
+        if (!last) last = pt_window(fn, fi, req[svals[p + 1]].ts).ws != w.ws;
+        if (last) atomicMax((long long*)&flows[f].fws[w.idx], (long long)w.ws);
+    }
+    okeys[p] = key;
+    ovals[p] = i;
+}
+
+__global__ __launch_bounds__(256) void k_ptok_gather(const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
+                                                     uint64_t n, uint32_t sent, const sg_param_token_req* __restrict__ req,
+                                                     int64_t* __restrict__ dts, int32_t* __restrict__ dacq) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || sk[p] >= sent) return;
+    const sg_param_token_req q = req[sv[p]];
+    dts[p] = q.ts;
+    dacq[p] = q.acquire_count;
+}
+
+__global__ __launch_bounds__(64) void k_ptok_chain(const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv,
+                                                   uint64_t n, uint32_t sent, const int64_t* __restrict__ dts,
+                                                   const int32_t* __restrict__ dacq, const PFlow* __restrict__ flows,
+                                                   const PHot* __restrict__ hot, PVal* __restrict__ tab,
+                                                   sg_token_result* __restrict__ res) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t s = sk[p];
+    if (s >= sent || (p > 0 && sk[p - 1] == s)) return;  // one lane per group start
+    PVal* pv = &tab[s];
+    const PFlow* F = &flows[pv->flow];
+    const int32_t fn = F->n < CP_MAXN ? F->n : CP_MAXN, interval = F->interval;
+    const double isec = interval / 1000.0;  // LeapArray.getIntervalInSecond
+    const double thr = pt_threshold(*F, hot, pv->key);
+    PtChain c;
+#pragma unroll
+    for (int j = 0; j < CP_MAXN; ++j) {
+        c.ws[j] = j < fn ? pv->ws[j] : -1;
+        c.cnt[j] = j < fn ? pv->cnt[j] : 0;
+    }
+    for (uint64_t e = p; e < n && sk[e] == s; ++e) {
+        const double next = pt_step(c, fn, interval, isec, thr, dts[e], dacq[e]);
+        sg_token_result o;
+        o.status = SG_TOKEN_BLOCKED; o.remaining = 0; o.wait_in_ms = 0; o.reserved = 0;
+        if (!(next < 0)) { o.status = SG_TOKEN_OK; o.remaining = j_d2i(next); }
+        res[sv[e]] = o;
+    }
+#pragma unroll
+    for (int j = 0; j < CP_MAXN; ++j)
+        if (j < fn) { pv->ws[j] = c.ws[j]; pv->cnt[j] = c.cnt[j]; }
+}
+
+hipError_t launch_ptok_prep(const sg_param_token_req* preq, uint64_t n, uint64_t n_values, sg_token_req* treq,
+                            unsigned long long* st, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_ptok_prep, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, preq, n, n_values, treq, st);
+    return hipGetLastError();
+}
+// the per-flow words of the call (serial: nflows words, zeroed here)
+hipError_t launch_ptok_elig(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
+                            const PFlow* flows, uint32_t nflows, uint32_t* serial, hipStream_t st) {
+    if (!n || !nflows) return hipSuccess;
+    hipError_t e = hipMemsetAsync(serial, 0, (size_t)nflows * 4, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ptok_elig, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, skeys, svals, n, req, flows,
+                       nflows, serial);
+    return hipGetLastError();
+}
+// The value-parallel owner over the flows whose word of `serial` is 0.  slotof / rep / ka / va / kb / vb: n-word
+// scratch arrays; dedup: dmask + 1 >= 2 n words; dts / dacq: n entries; hist / part: the radix sort's (kernels.hip).
+hipError_t launch_ptok_vp(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
+                          const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
+                          uint32_t mask, const uint32_t* serial, uint32_t* dedup, uint32_t dmask, uint32_t* slotof,
+                          uint32_t* rep, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, int64_t* dts,
+                          int32_t* dacq, uint32_t* hist, uint32_t* part, uint32_t tile, sg_token_result* res,
+                          uint32_t* flags, unsigned long long* ctr,
+                          hipError_t (*rhist)(const uint32_t*, uint64_t, int, uint32_t*, uint32_t, hipStream_t),
+                          hipError_t (*rscatter)(const uint32_t*, const uint32_t*, uint64_t, int, const uint32_t*, uint32_t,
+                                                 uint32_t*, uint32_t*, uint32_t*, hipStream_t),
+                          hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
+                          hipStream_t st) {
+    if (!n || !nflows) return hipSuccess;
+    const uint32_t g = (uint32_t)((n + 255) / 256);
+    hipError_t e = hipMemsetAsync(dedup, 0xFF, ((size_t)dmask + 1) * 4, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ptok_lookup, dim3(g), dim3(256), 0, st, skeys, svals, n, req, values, nflows, serial, tab, mask,
+                       dedup, dmask, slotof, rep);
+    hipLaunchKernelGGL(k_ptok_claim, dim3(g), dim3(256), 0, st, skeys, svals, n, req, values, tab, mask, slotof, rep,
+                       flags);
+    const uint32_t sent = mask + 1;  // keys 0 .. mask are slots
+    hipLaunchKernelGGL(k_ptok_keys, dim3(g), dim3(256), 0, st, skeys, svals, n, req, flows, nflows, serial, slotof, rep,
+                       sent, ka, va, res, ctr);
+    int bits = 1;
+    while (bits < 32 && (1ull << bits) <= sent) ++bits;
+    const int passes = (bits + 7) / 8;
+    const uint32_t nblocks = (uint32_t)((n + tile - 1) / tile);
+    for (int p = 0; p < passes; ++p) {
+        if ((e = rhist(ka, n, p * 8, hist, nblocks, st)) != hipSuccess) return e;
+        if ((e = scan(hist, hist, (uint64_t)nblocks * 256, part, nullptr, st)) != hipSuccess) return e;
+        if ((e = rscatter(ka, va, n, p * 8, hist, nblocks, kb, vb, nullptr, st)) != hipSuccess) return e;
+        uint32_t* t = ka; ka = kb; kb = t;
+        t = va; va = vb; vb = t;
+    }
+    hipLaunchKernelGGL(k_ptok_gather, dim3(g), dim3(256), 0, st, ka, va, n, sent, req, dts, dacq);
+    hipLaunchKernelGGL(k_ptok_chain, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, ka, va, n, sent, dts, dacq, flows,
+                       hot, tab, res);
     return hipGetLastError();
 }
 

@@ -196,7 +196,23 @@ hipError_t launch_tok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_
                            hipStream_t hs, hipEvent_t fork, hipEvent_t join);
 hipError_t launch_ptok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
                             const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
-                            uint32_t mask, sg_token_result* res, uint32_t* flags, hipStream_t st);
+                            uint32_t mask, sg_token_result* res, uint32_t* flags, const uint32_t* serial,
+                            unsigned long long* ctr, hipStream_t st);
+hipError_t launch_ptok_prep(const sg_param_token_req* preq, uint64_t n, uint64_t n_values, sg_token_req* treq,
+                            unsigned long long* st, hipStream_t s);
+hipError_t launch_ptok_elig(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
+                            const PFlow* flows, uint32_t nflows, uint32_t* serial, hipStream_t st);
+hipError_t launch_ptok_vp(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
+                          const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
+                          uint32_t mask, const uint32_t* serial, uint32_t* dedup, uint32_t dmask, uint32_t* slotof,
+                          uint32_t* rep, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, int64_t* dts,
+                          int32_t* dacq, uint32_t* hist, uint32_t* part, uint32_t tile, sg_token_result* res,
+                          uint32_t* flags, unsigned long long* ctr,
+                          hipError_t (*rhist)(const uint32_t*, uint64_t, int, uint32_t*, uint32_t, hipStream_t),
+                          hipError_t (*rscatter)(const uint32_t*, const uint32_t*, uint64_t, int, const uint32_t*, uint32_t,
+                                                 uint32_t*, uint32_t*, uint32_t*, hipStream_t),
+                          hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
+                          hipStream_t st);
 hipError_t launch_pv_rehash(const PVal* src, uint64_t n_src, const PFlow* flows, uint32_t nflows, PVal* dst,
                             uint32_t dmask, uint32_t* out, hipStream_t st);
 // keysweep.hip
@@ -766,6 +782,15 @@ struct sg_engine {
     sg_param_token_req* d_preq = nullptr;
     uint64_t* d_pvals = nullptr;
     uint64_t pcap = 0, pvcap = 0;
+    // the value-parallel owner (ptok.h): SG_PTOK_VP=0 leaves every flow to k_ptok_flow, SG_PTOK_MIN = the request
+    // count below which a call with fewer than PTOK_PER_FLOW requests per loaded flow does (and keeps the one-wave
+    // limiter: the parent's launches, measured faster there); d_ptst: [0] listed values and [1] flags of the call (k_ptok_prep), [2..4] the
+    // cumulative owner counters (sg_cluster_param_table_stats [7..9]); the per-flow words and the dedup table
+    bool ptok_vp = true;
+    uint64_t ptok_min = 8192;
+    unsigned long long* d_ptst = nullptr;
+    uint32_t *d_ptserial = nullptr, *d_ptdedup = nullptr;
+    uint64_t ptserial_cap = 0, ptdedup_cap = 0;
     // exact parameter keys (pkeys.h): the value dictionary of sg_param_intern, the entries the loaded param rules'
     // hot items pin, and the sweep's device buffers (keysweep.hip) and statistics (sg_param_keys_stats)
     pk::Dict<pk::StdHash> pkeys;
@@ -1478,6 +1503,8 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (const char* v = std::getenv("SG_PQ")) e->pq_on = v[0] != '0';
     if (const char* v = std::getenv("SG_MIX")) e->mix_on = v[0] != '0';
     if (const char* v = std::getenv("SG_MIX_PQ")) e->mix_pq = v[0] != '0';
+    if (const char* v = std::getenv("SG_PTOK_VP")) e->ptok_vp = v[0] != '0';
+    if (const char* v = std::getenv("SG_PTOK_MIN")) e->ptok_min = std::strtoull(v, nullptr, 0);
     if (const char* v = std::getenv("SG_PV_PQ")) e->pv_pq = v[0] != '0';
     if (const char* v = std::getenv("SG_PV")) e->pv_on = v[0] != '0';
     e->pvt_on = e->pv_on;
@@ -1639,7 +1666,7 @@ int sg_engine_destroy(sg_engine* e) {
     dfree(e->d_snap_cnt); dfree(e->d_snap_off); dfree(e->d_snap_out); dfree(e->d_dbg);
     dfree(e->d_ks_key); dfree(e->d_ks_idx); dfree(e->d_ks_marks);
     for (auto& v : e->ks_ev) if (v) (void)hipEventDestroy(v);
-    dfree(e->d_pvcnt); dfree(e->d_pvspare);
+    dfree(e->d_pvcnt); dfree(e->d_pvspare); dfree(e->d_ptst); dfree(e->d_ptserial); dfree(e->d_ptdedup);
     for (auto& v : e->pv_ev) if (v) (void)hipEventDestroy(v);
     for (auto& s : e->evset)
         for (auto& v : s) if (v) (void)hipEventDestroy(v);
@@ -1787,6 +1814,14 @@ int sg_cluster_param_table_stats(sg_engine* e, uint64_t* out, int cap) {
                            e->pv_resizes, e->pv_last_us, 1ull << e->pv_max_log2};
     int k = 0;
     for (; k < cap && k < 7; ++k) out[k] = v[k];
+    if (cap > 7) {  // the owners' counters live on the device (every call has returned: nothing is in flight)
+        unsigned long long c[3] = {0, 0, 0};
+        if (e->d_ptst && hipMemcpy(c, e->d_ptst + 2, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            return k;
+        }
+        for (; k < cap && k < 10; ++k) out[k] = c[k - 7];
+    }
     return k;
 }
 // diagnostics export: the last sweep's scans in ms {maps, key ring, token server values}
@@ -3892,25 +3927,22 @@ static int pv_make_room(sg_engine* e, uint64_t V) {
 }
 
 // Batched DefaultTokenService.requestParamToken: the flow path's classify and namespace limiter steps on a
-// derived sg_token_req view (n_values == 0 -> acquire 0 -> BAD_REQUEST), then k_ptok_flow per param flow.
+// derived sg_token_req view (k_ptok_prep; n_values == 0 -> acquire 0 -> BAD_REQUEST), then per param flow either
+// the value-parallel owner (ptok.h, launch_ptok_vp) or k_ptok_flow (k_ptok_elig decides which, on the device).
+// reqs, values and out may each be host or device memory: everything is copied into the engine's buffers first.
 int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs, uint64_t n, const uint64_t* values,
                                     uint64_t n_values, sg_token_result* out) {
     if (!e || (n && (!reqs || !out)) || (n_values && !values)) return fail(SG_EINVAL, "null argument");
     if (!n) return SG_OK;
     if (n > 0x7FFFFFFFull) return fail(SG_EINVAL, "too many token requests in one call");
-    uint64_t listed = 0;  // values the requests list: the call claims at most that many value slots
-    for (uint64_t i = 0; i < n; ++i) {
-        if (reqs[i].value_off > n_values || reqs[i].n_values > n_values - reqs[i].value_off)
-            return fail(SG_EINVAL, "param token request values out of range");
-        listed += reqs[i].n_values;
-    }
     if (int rc = drain(e)) return rc;
-    if (int rc = pv_make_room(e, listed)) return rc;  // before the limiter or any window moves
     hipStream_t st = e->stream;
     int rc = ensure_batch(e, n);
     if (rc) return rc;
     if (n > e->tcap) {
         dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx);
+        e->d_treq = nullptr; e->d_tres = nullptr; e->d_tfidx = nullptr;
+        e->tcap = 0;
         uint64_t c = std::max<uint64_t>(n, 1u << 16);
         HIPCHK(hipMalloc(&e->d_treq, c * sizeof(sg_token_req)));
         HIPCHK(hipMalloc(&e->d_tres, c * sizeof(sg_token_result)));
@@ -3919,13 +3951,41 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
     }
     if (n > e->pcap) {
         dfree(e->d_preq);
-        e->pcap = std::max<uint64_t>(n, 1u << 16);
-        HIPCHK(hipMalloc(&e->d_preq, e->pcap * sizeof(sg_param_token_req)));
+        e->d_preq = nullptr;
+        e->pcap = 0;
+        const uint64_t c = std::max<uint64_t>(n, 1u << 16);
+        HIPCHK(hipMalloc(&e->d_preq, c * sizeof(sg_param_token_req)));
+        e->pcap = c;
     }
     if (n_values > e->pvcap) {
         dfree(e->d_pvals);
-        e->pvcap = std::max<uint64_t>(n_values, 1u << 16);
-        HIPCHK(hipMalloc(&e->d_pvals, e->pvcap * sizeof(uint64_t)));
+        e->d_pvals = nullptr;
+        e->pvcap = 0;
+        const uint64_t c = std::max<uint64_t>(n_values, 1u << 16);
+        HIPCHK(hipMalloc(&e->d_pvals, c * sizeof(uint64_t)));
+        e->pvcap = c;
+    }
+    if (!e->d_ptst) {
+        HIPCHK(hipMalloc(&e->d_ptst, 8 * sizeof(unsigned long long)));
+        HIPCHK(hipMemset(e->d_ptst, 0, 8 * sizeof(unsigned long long)));
+    }
+    const uint32_t nflows = (uint32_t)e->pflows.size();
+    if (nflows > e->ptserial_cap) {
+        dfree(e->d_ptserial);
+        e->d_ptserial = nullptr;
+        e->ptserial_cap = 0;
+        const uint64_t c = std::max<uint64_t>(nflows, 1u << 12);
+        HIPCHK(hipMalloc(&e->d_ptserial, c * 4));
+        e->ptserial_cap = c;
+    }
+    uint64_t dcap = 1u << 12;  // the dedup table: a power of two of at least twice the call's requests
+    while (dcap < 2 * n) dcap <<= 1;
+    if (dcap > e->ptdedup_cap) {
+        dfree(e->d_ptdedup);
+        e->d_ptdedup = nullptr;
+        e->ptdedup_cap = 0;
+        HIPCHK(hipMalloc(&e->d_ptdedup, dcap * 4));
+        e->ptdedup_cap = dcap;
     }
     if (int rc2 = ensure_ns(e)) return rc2;
     if (!e->d_pftab) {  // no cluster param rule loaded yet: an empty table
@@ -3935,33 +3995,43 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
         HIPCHK(hipMemcpy(e->d_pftab, t, sizeof(t), hipMemcpyHostToDevice));
         e->pftab_mask = 15;
     }
-    std::vector<sg_token_req> tq(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        tq[i].ts = reqs[i].ts;
-        tq[i].flow_id = reqs[i].flow_id;
-        tq[i].acquire_count = reqs[i].n_values ? reqs[i].acquire_count : 0;  // empty params -> badRequest
-        tq[i].prioritized = 0;
-    }
-    const uint32_t nflows = (uint32_t)e->pflows.size();
-    HIPCHK(hipMemcpyAsync(e->d_treq, tq.data(), n * sizeof(sg_token_req), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->d_preq, reqs, n * sizeof(sg_param_token_req), hipMemcpyHostToDevice, st));
-    if (n_values) HIPCHK(hipMemcpyAsync(e->d_pvals, values, n_values * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    // the request view, the range check and the listed values, on the device, then the classify step (it writes
+    // the call's own arrays only); (range flag, listed) and the order flag are read once, before anything moves
+    HIPCHK(hipMemcpyAsync(e->d_preq, reqs, n * sizeof(sg_param_token_req), hipMemcpyDefault, st));
+    if (n_values) HIPCHK(hipMemcpyAsync(e->d_pvals, values, n_values * sizeof(uint64_t), hipMemcpyDefault, st));
+    HIPCHK(hipMemsetAsync(e->d_ptst, 0, 2 * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(e->d_small, 0, 4, st));
+    HIPCHK(launch_ptok_prep(e->d_preq, n, n_values, e->d_treq, e->d_ptst, st));
     const uint32_t nns = (uint32_t)e->ns_names.size();
     const bool grouped = nns > 1 || e->tok_ns;
     HIPCHK(launch_tok_classify(e->d_treq, n, e->d_pftab, e->pftab_mask, e->d_tfidx, e->d_tres, e->d_small,
                                grouped ? e->d_k0 : nullptr, grouped ? e->d_v0 : nullptr, nns, st));
+    unsigned long long head[2] = {0, 0};
     uint32_t flags = 0;
+    HIPCHK(hipMemcpyAsync(head, e->d_ptst, sizeof(head), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&flags, e->d_small, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (head[1] & 1) return fail(SG_EINVAL, "param token request values out of range");
     if (flags & 1) return fail(SG_EINVAL, "token requests must be ordered by ts (the replay clock)");
+    const uint64_t listed = head[0];  // the call claims at most that many value slots
+    if (int rc2 = pv_make_room(e, listed)) return rc2;  // before the limiter or any window moves
     const double allowed = e->ns_limit[0] < 0 ? 1.0 / 0.0 : e->ns_limit[0];
     uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
+    // A small call spread thinly over many flows (fewer than SG_PTOK_MIN requests and fewer than PTOK_PER_FLOW per
+    // loaded flow) keeps the one-wave limiter and k_ptok_flow for every flow: fewer launches than the parallel
+    // limiter and the value-parallel owner need, and a lane's walk is short there (measured).
+    constexpr uint64_t PTOK_PER_FLOW = 8;
+    const bool small = n < e->ptok_min && n < PTOK_PER_FLOW * nflows;
+    const bool lane_only = !e->ptok_vp || small;
     if (grouped) {
         if (int rc2 = tok_limiter_grouped(e, n, nflows, kin, vin, kout, vout)) return rc2;
-    } else
+    } else if (small)
         HIPCHK(launch_tok_limiter(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0, e->d_tres,
                                   st));
+    else
+        HIPCHK(launch_tok_limiter_par(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0,
+                                      e->d_tres, e->d_flag, e->d_pos, e->d_order, e->d_prev, e->d_dec, e->d_posof,
+                                      e->d_part, e->d_small + 8, launch_scan, st));
     if (nflows) {
         int bits = 1;
         while (bits < 32 && (1ull << bits) <= nflows) ++bits;
@@ -3975,10 +4045,22 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
             std::swap(vin, vout);
         }
         e->pv_claimed += listed;
-        HIPCHK(launch_ptok_flow(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab,
-                                e->pv_mask, e->d_tres, e->d_small, st));
+        if (lane_only)
+            HIPCHK(launch_ptok_flow(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab,
+                                    e->pv_mask, e->d_tres, e->d_small, nullptr, e->d_ptst + 2, st));
+        else {
+            // who decides which flow; the two owners then work on disjoint flows (the limiter's scratch arrays are free)
+            HIPCHK(launch_ptok_elig(kin, vin, n, e->d_preq, e->d_pflow, nflows, e->d_ptserial, st));
+            HIPCHK(launch_ptok_flow(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab,
+                                    e->pv_mask, e->d_tres, e->d_small, e->d_ptserial, nullptr, st));
+            HIPCHK(launch_ptok_vp(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab, e->pv_mask,
+                                  e->d_ptserial, e->d_ptdedup, (uint32_t)(dcap - 1), e->d_flag, e->d_pos, e->d_order,
+                                  e->d_prev, e->d_dec, e->d_posof, reinterpret_cast<int64_t*>(e->d_cand),
+                                  reinterpret_cast<int32_t*>(e->d_out), e->d_hist, e->d_part, radix_tile(), e->d_tres,
+                                  e->d_small, e->d_ptst + 2, launch_radix_hist, launch_radix_scatter, launch_scan, st));
+        }
     }
-    HIPCHK(hipMemcpyAsync(out, e->d_tres, n * sizeof(sg_token_result), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out, e->d_tres, n * sizeof(sg_token_result), hipMemcpyDefault, st));
     HIPCHK(hipMemcpyAsync(&flags, e->d_small, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (flags & 2) return fail(SG_ENOMEM, "cluster param value table is full");

@@ -244,6 +244,65 @@ def request_tokens_tensor(reqs: "torch.Tensor", decide_ptr=None, server: int = 0
     return res[off * rs: (off + n) * rs]
 
 
+def request_param_tokens_tensor(reqs: "torch.Tensor", values: "torch.Tensor", decide_ptr=None, server: int = 0,
+                                group=None) -> "torch.Tensor":
+    """The param twin of request_tokens_tensor: ``reqs`` = this rank's A.PARAM_TOKEN_REQ_DTYPE rows (time-ordered)
+    as a uint8 tensor and ``values`` = the uint64 keys they name (an int64 or uint8 tensor of the same bits, indexed
+    by the rows' value_off) on the group's device; returns this rank's A.TOKEN_RES_DTYPE rows as a uint8 tensor
+    there.  Rows and values are all-gathered, every rank's value_off is rebased by the values of the ranks before
+    it, the server rank orders the rows by a stable sort on ts ((ts, rank, index) order) and decides them in one call
+    of ``decide_ptr(req_ptr, n, values_ptr, n_values, out_ptr)`` (``Engine.cluster_request_param_ptr``), and the
+    results are broadcast.  Nothing goes through host memory under RCCL.  Collective."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    rq, rs = A.PARAM_TOKEN_REQ_DTYPE.itemsize, A.TOKEN_RES_DTYPE.itemsize
+    voff = A.PARAM_TOKEN_REQ_DTYPE.fields["value_off"][1]
+    dev = reqs.device
+    reqs = reqs.contiguous().view(torch.uint8).reshape(-1)
+    values = values.contiguous().view(torch.uint8).reshape(-1)
+    n, nv = reqs.numel() // rq, values.numel() // 8
+    cnt = torch.tensor([n, nv], dtype=torch.int64, device=dev)
+    cnts = [torch.zeros_like(cnt) for _ in range(world)]
+    dist.all_gather(cnts, cnt, group=group)
+    cnts = [c.tolist() for c in cnts]
+    ns, nvs = [int(c[0]) for c in cnts], [int(c[1]) for c in cnts]
+    total, total_v = sum(ns), sum(nvs)
+    if total == 0:
+        return torch.zeros(0, dtype=torch.uint8, device=dev)
+    width = max(ns) * rq + max(nvs) * 8  # one gather: a rank's rows, then its values
+    mine = torch.zeros(width, dtype=torch.uint8, device=dev)
+    mine[: n * rq] = reqs
+    mine[max(ns) * rq: max(ns) * rq + nv * 8] = values
+    outs = [torch.empty(width, dtype=torch.uint8, device=dev) for _ in range(world)]
+    dist.all_gather(outs, mine, group=group)
+    res = torch.zeros(total * rs, dtype=torch.uint8, device=dev)
+    if rank == server:
+        if decide_ptr is None:
+            raise ValueError("the token-server rank needs a decide function")
+        parts, base = [], 0
+        for r in range(world):
+            rows = outs[r][: ns[r] * rq].clone().view(ns[r], rq)
+            if ns[r]:
+                off = rows[:, voff: voff + 8].contiguous().view(torch.int64).view(-1) + base
+                rows[:, voff: voff + 8] = off.view(-1, 1).view(torch.uint8)
+            parts.append(rows)
+            base += nvs[r]
+        allq = torch.cat(parts)
+        allv = torch.cat([outs[r][max(ns) * rq: max(ns) * rq + nvs[r] * 8] for r in range(world)]).contiguous()
+        if total_v == 0:
+            allv = torch.zeros(8, dtype=torch.uint8, device=dev)  # (a valid pointer for a call that names no value)
+        ts = allq[:, :8].contiguous().view(torch.int64).view(-1)
+        order = torch.sort(ts, stable=True).indices
+        q = allq.index_select(0, order).contiguous()
+        out = torch.empty((total, rs), dtype=torch.uint8, device=dev)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)  # (the engine's own stream reads q and allv)
+        decide_ptr(q.data_ptr(), total, allv.data_ptr(), total_v, out.data_ptr())
+        res.view(total, rs).index_copy_(0, order, out)
+    dist.broadcast(res, src=server, group=group)
+    off = sum(ns[:rank])
+    return res[off * rs: (off + n) * rs]
+
+
 def request_tokens(reqs: np.ndarray, decide=None, server: int = 0, group=None) -> np.ndarray:
     """Token requests of this rank (A.TOKEN_REQ_DTYPE, time-ordered) -> results (A.TOKEN_RES_DTYPE).
 

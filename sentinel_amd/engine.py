@@ -435,6 +435,12 @@ class Engine:
                                                      len(values), out.ctypes.data))
         return out
 
+    def cluster_request_param_ptr(self, req_ptr: int, n: int, values_ptr: int, n_values: int, out_ptr: int):
+        """Device (or host) buffers: n A.PARAM_TOKEN_REQ_DTYPE rows at req_ptr and n_values uint64 keys at values_ptr
+        -> A.TOKEN_RES_DTYPE rows at out_ptr."""
+        _check(lib().sg_cluster_request_param_tokens(self.h, C.c_void_p(req_ptr), n, C.c_void_p(values_ptr), n_values,
+                                                     C.c_void_p(out_ptr)))
+
     def cluster_request_param(self, reqs):
         """reqs: list of (ts, flow_id, acquire, [value keys]) -> list of (status, remaining, wait)."""
         arr, vals = A.param_token_arrays(reqs)
@@ -449,3 +455,13 @@ class Engine:
         k = lib().sg_cluster_param_table_stats(self.h, out, 7)
         names = ("capacity", "claimed_ub", "live_kept", "rehashes", "resizes", "rehash_us", "max_capacity")
         return {names[i]: int(out[i]) for i in range(k)}
+
+    def cluster_param_owner_stats(self) -> dict:
+        """Who decided the flow-stage requests of cluster_request_param so far (sg_cluster_param_table_stats [7..9]):
+        the value-parallel owner (one lane per (flowId, value) chain), the one-lane-per-flow owner, and how many
+        times a flow stayed with the latter because a call held a multi-value request of it or began before one of
+        its window stamps.  SG_PTOK_VP=0 leaves every flow to the one-lane owner."""
+        out = (C.c_uint64 * 10)()
+        k = lib().sg_cluster_param_table_stats(self.h, out, 10)
+        names = ("value_parallel_requests", "flow_lane_requests", "flows_kept_serial")
+        return {names[i - 7]: int(out[i]) for i in range(7, k)}
