@@ -170,7 +170,11 @@ typedef struct sg_authority_rule {
 /* ---- events ----------------------------------------------------------------
  * One 24-byte record per SphU.entry / Entry.exit / Tracer.trace, in
  * non-decreasing ts order (ties keep submission order).  ts is the value
- * TimeUtil.currentTimeMillis() had at the event (core/util/TimeUtil.java:49). */
+ * TimeUtil.currentTimeMillis() had at the event (core/util/TimeUtil.java:49).
+ * One batch spans at most SG_MAX_BATCH_SPAN_MS: its last ts minus its first
+ * (the kernels keep an event's time as a 32-bit offset from the batch's first
+ * event).  The limit is per batch; any time may pass between two batches. */
+#define SG_MAX_BATCH_SPAN_MS 0x7FFFFFFFll /* 2^31 - 1 ms, 24.8 days */
 enum {
     SG_EV_ENTRY = 0,  /* SphU.entry(name, type, count, args...)   core/SphU.java:202 */
     SG_EV_EXIT = 1,   /* Entry.exit(count[, args])                core/Entry.java:78-103 */
@@ -408,6 +412,15 @@ int sg_param_keys_stats(sg_engine* e, uint64_t* out, int cap);
  * EXIT and ClusterNode.trace (core/node/ClusterNode.java:99-106) for every TRACE,
  * in event order per resource.  ev and out may be host or device pointers
  * (device pointers avoid the PCIe copy).  sg_submit is synchronous.
+ *
+ * A malformed batch returns SG_EINVAL (sg_last_error() says which): a res_id
+ * at or above max_resources, a ts below the one before it, a last ts more than
+ * SG_MAX_BATCH_SPAN_MS after the first ("a batch must span less than 2^31 ms"),
+ * an EXIT / TRACE whose aux names no earlier ENTRY of its resource, an ext row
+ * outside the argument table.  Such a batch is refused whole, before any of it
+ * is decided, and refusing it is a no-op: no window, rule state, thread count or
+ * parameter map moves and it takes no event indices (out holds nothing of
+ * use).  The same batch split where the span ends is accepted.
  *
  * sg_submit_async returns once the batch's group stage is queued; the batch is
  * not checked yet.  The next call that touches the engine -- another submit,

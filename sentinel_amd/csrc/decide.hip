@@ -2652,7 +2652,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                     const int64_t nlo = sh.bkt0 * 500 - t0, nrs = sh.next_reset - t0;
                     const int64_t nhi = (nrs < nlo + 500) ? nrs : nlo + 500;
                     sh.mrlo = (int32_t)nlo;
-                    sh.mrhi = nhi > (int64_t)INT32_MAX ? INT32_MAX : (int32_t)nhi;
+                    // mrhi: the round's last millisecond (inclusive: a round that holds dt = INT32_MAX, the largest
+                    // time of a batch, has no 32-bit exclusive end; clamped there an event at INT32_MAX was past every
+                    // round and the machine opened its round again without end).  probe_at's "no position" is INT32_MAX
+                    // too: in a round that holds dt = INT32_MAX, and only there, it reads as "still in the round", so a
+                    // frozen round there counts as long and leaves the machine for the frozen-stretch code -- always
+                    // valid, slower for that one round
+                    sh.mrhi = nhi - 1 > (int64_t)INT32_MAX ? INT32_MAX : (int32_t)(nhi - 1);
                     for (int s = 0; s < nf; ++s) {
                         const DRule& r = sh.rules[s];
                         double l = r.count;
@@ -2778,7 +2784,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                         for (int k = 0; k < nd; ++k) anyc |= sh.rs[nf + k].a != 0;
                         const bool cut0 = nd > 0 && sh.rs[nf].a != 0;
                         if (sat || cut0) {
-                            if (pr_dt < sh.mrhi) sh.mmode = 2;  // long: the frozen-stretch code skips it
+                            if (pr_dt <= sh.mrhi) sh.mmode = 2;  // long: the frozen-stretch code skips it
                             else m_frozen(p, P);
                         } else if (!anyc) m_open(p);
                         else sh.mmode = 2;
@@ -2819,7 +2825,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                                 const uint32_t code = (rr[k].w >> 16) & 0xFFu;
                                 uint32_t c = 0;
                                 if (q < olo) c = 0;
-                                else if (q >= sg.len || edt >= rhi || edt < rlo) c = 0x80u;
+                                else if (q >= sg.len || edt > rhi || edt < rlo) c = 0x80u;
                                 else if (ek == SG_EV_ENTRY) c = ((rr[k].w >> 8) & RF_PBLK) ? JC_PB : JC_ENT;
                                 else {
                                     bool eff = code == RC_NONE || code == RC_PASSED;
@@ -3075,7 +3081,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                                 continue;
                             }
                             const int64_t Pf = uni64(sh.os_P);
-                            if (MACH && o_f < (uint32_t)nf && msat(Pf) && pr_dt >= (int32_t)uni((uint32_t)sh.mrhi)) {
+                            if (MACH && o_f < (uint32_t)nf && msat(Pf) && pr_dt > (int32_t)uni((uint32_t)sh.mrhi)) {
                                 // the quota is spent: frozen until the round ends
                                 if (tid == 0) {
                                     m_seg();
@@ -3111,7 +3117,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                             const int32_t edt = (int32_t)rr[k].x;
                             const uint32_t ek = rr[k].w & 0xFFu, ec = rr[k].z & 0xFFFFu;
                             const bool act = q >= fz0 && q < sg.len;
-                            const bool in = edt >= rlo && edt < rhi;
+                            const bool in = edt >= rlo && edt <= rhi;
                             const double curv = (double)j_iadd(fzi, (int)ec);
                             uint32_t bs = (uint32_t)nf;  // the blocking flow stage (nf: none)
 #pragma unroll

@@ -365,10 +365,11 @@ __device__ __forceinline__ void head_seg(HdShared& sh, const SEv* __restrict__ r
                         kcur = 0;
                     }
                     const int64_t se = T + 1000 - t0;  // the second's end, relative
-                    const int32_t sei = se > 0x7FFFFFFF ? 0x7FFFFFFF : (int32_t)se;
+                    const bool sin = se <= 0x7FFFFFFF;  // (else no time of the batch is past it, dt = INT32_MAX included)
+                    const int32_t sei = sin ? (int32_t)se : 0x7FFFFFFF;
                     uint32_t after = 0;  // the lane's active positions at or past it
 #pragma unroll
-                    for (uint32_t e = 0; e < HD_EP; ++e) after |= (uint32_t)(dtr[e] >= sei) << e;
+                    for (uint32_t e = 0; e < HD_EP; ++e) after |= (uint32_t)(sin && dtr[e] >= sei) << e;
                     after &= amask;
                     const uint64_t ab = __ballot(after != 0);
                     if (ab) {
@@ -500,8 +501,10 @@ __device__ __forceinline__ void head_seg(HdShared& sh, const SEv* __restrict__ r
                 const int32_t lq = lq64 > (1 << 30) ? (1 << 30) : lq64 < -(1 << 30) ? -(1 << 30) : (int32_t)lq64;
                 const int32_t ci = (int32_t)cost1;
                 const float rc = 1.0f / (float)ci;
+                // (t reaches INT32_MAX: with lq < 0, t - lq is taken at the largest t that fits -- past the clamp below)
+                const int32_t tfit = lq < 0 ? INT32_MAX + lq : INT32_MAX;
                 auto lat = [&](int32_t t) -> int32_t {  // max(0, floor((t - lq) / cost)), exact
-                    int32_t x = t - lq;
+                    int32_t x = (t < tfit ? t : tfit) - lq;
                     x = x < 0 ? -1 : x > (1 << 30) ? (1 << 30) : x;
                     int32_t k = (int32_t)((float)x * rc);
                     k = k * ci > x ? k - 1 : k;
@@ -734,7 +737,8 @@ __device__ __forceinline__ void head_seg(HdShared& sh, const SEv* __restrict__ r
 #pragma unroll
                 for (uint32_t e = 0; e < HD_EP; ++e) dl = ((vmask >> e) & 1) ? dt[e] : dl;
                 const int32_t dlast = __builtin_amdgcn_readlane(dl, ll);
-                auto bkt_of = [&](int32_t d) -> int32_t { const int32_t x = d + toff; return x >= 0 ? x / 500 : -((499 - x) / 500); };
+                // (0 <= d <= INT32_MAX and toff < 500: the sum fits in 32 unsigned bits, not in signed ones)
+                auto bkt_of = [&](int32_t d) -> int32_t { return (int32_t)(((uint32_t)d + (uint32_t)toff) / 500u); };
                 const int32_t bf = bkt_of(dfirst);
                 if (bf == bkt_of(dlast) && __ballot(c1 != 0) == 0) {
                     const int64_t b = tb0 + bf;
@@ -774,11 +778,12 @@ __device__ __forceinline__ void head_seg(HdShared& sh, const SEv* __restrict__ r
                             fold();
                             cb = b;
                         }
-                        const int32_t lo_dt = brel * 500 - toff, hi_dt = lo_dt + 500;  // the bucket's relative times
+                        const uint32_t lo_u = (uint32_t)brel * 500u - (uint32_t)toff;  // the bucket's first relative time
                         uint32_t sP = 0, sB = 0, sS = 0, sRT = 0, sE = 0, sT = 0, sMin = HD_NONE;
 #pragma unroll
                         for (uint32_t e = 0; e < HD_EP; ++e) {
-                            const bool in = ((left >> e) & 1) && dt[e] >= lo_dt && dt[e] < hi_dt;
+                            // (unsigned: an earlier time wraps past 500, and the bucket's end may lie past INT32_MAX)
+                            const bool in = ((left >> e) & 1) && (uint32_t)dt[e] - lo_u < 500u;
                             const uint32_t cnt = cz[e] & 0xFFFFu, rtv = cz[e] >> 16;
                             const bool ent = in && ((emask >> e) & 1), ps = ent && ((st >> e) & 1);
                             const bool x = in && ((xe & xk) >> e) & 1, t = in && ((xe & tk) >> e) & 1 && cnt > 0;
