@@ -162,7 +162,7 @@ __device__ __forceinline__ uint32_t wave_alloc(uint32_t* ctr, uint32_t k) {  // 
 }
 __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const uint32_t* __restrict__ mp, uint64_t n,
                                                  const Prog* __restrict__ prog, const uint32_t* __restrict__ prio,
-                                                 uint32_t lane_max, uint32_t j1_max,
+                                                 uint32_t lane_max, uint32_t lite_max, uint32_t j1_max,
                                                  uint32_t j4_max, uint32_t force_lane, uint32_t* __restrict__ blkcnt,
                                                  uint32_t nblk, uint32_t pq_ok, uint32_t pq_wide, uint32_t* __restrict__ aux,
                                                  uint32_t* __restrict__ ashort, uint64_t* __restrict__ along,
@@ -196,8 +196,18 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
         const int nr = p.multi ? 16 : p.n_param + p.n_flow + p.n_degrade;  // PX_*: decided with 16-rule lanes
         // XF_MIX: the param checks run in k_pq's pre pass (args[0] from the key ring: no argument lists)
         const bool mixp = (p.xf & XF_MIX) && pq && mix && !(pm & PM_ARGL);
+        // k_lite: no param rules, <= 2 DefaultController flow stages (QPS or thread), <= 2 breakers
+        // (or one QPS DefaultController param rule on args[0] before them, scalar args: k_lite<true>), every
+        // flow stage on the ClusterNode (PF_SERIAL: a rule of another strategy, e.g. one whose node is never
+        // selected, FlowRuleChecker.selectReferenceNode, is k_lane's)
+        const bool lite = (p.n_param == 0 || ((p.xf & XF_PLITE) && !(pm & PM_ARGL))) && !p.multi && !lane_only &&
+                          (p.pflags & PF_J16) && !(p.pflags & (PF_WARM | PF_SERIAL));
+        // the lane bins keep a segment up to lane_max events; k_lite's programs without param rules up to lite_max
+        // (a full batch: 512 against 256, engine.cpp lite_max -- measured on C4 and C2; k_lane's programs keep
+        // lane_max: C3 with 512 for every program 6.0 -> 9.0 ms a batch)
+        const uint32_t lmax = (lite && p.n_param == 0) ? lite_max : lane_max;
         // single-rule THREAD-grade / rate-limiter heads (head.hip k_head) leave the lane bins from head_min events on
-        const uint32_t cmin = (head_min && (p.xf & (XF_HEADT | XF_HEADR)) && head_min < lane_max) ? head_min : lane_max;
+        const uint32_t cmin = (head_min && (p.xf & (XF_HEADT | XF_HEADR)) && head_min < lmax) ? head_min : lmax;
         const bool coop = !force_lane && !(p.pflags & PF_SERIAL) && (p.n_param == 0 || mixp) && sg.len > cmin &&
                           !lane_only && !p.multi;
         if (coop && p.n_param) mixk = sg.len > mix_wide ? 2u : 1u;  // (wide: pvalue.hip's passes, where on)
@@ -220,12 +230,6 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
         else {
             int lb = 31 - __clz(sg.len | 1);
             if (lb > (int)LANE_BINS - 1) lb = LANE_BINS - 1;
-            // k_lite: no param rules, <= 2 DefaultController flow stages (QPS or thread), <= 2 breakers
-            // (or one QPS DefaultController param rule on args[0] before them, scalar args: k_lite<true>), every
-            // flow stage on the ClusterNode (PF_SERIAL: a rule of another strategy, e.g. one whose node is never
-            // selected, FlowRuleChecker.selectReferenceNode, is k_lane's)
-            const bool lite = (p.n_param == 0 || ((p.xf & XF_PLITE) && !(pm & PM_ARGL))) && !p.multi && !lane_only &&
-                              (p.pflags & PF_J16) && !(p.pflags & (PF_WARM | PF_SERIAL));
             bin = (lite ? BIN_LITE : (nr <= 4 && !inline_aux) ? BIN_LANE : BIN_LANE16) + (LANE_BINS - 1 - lb);
         }
         // k_lane<16> keeps a PM_AUX resource's nodes inline; on every other owner the post-pass does
@@ -4140,15 +4144,16 @@ hipError_t launch_block_sums(const SEv* recs, uint64_t n, uint32_t* bst, Link* l
 }
 // mp: the segment count on the device; mb: an upper bound of it (the grid)
 hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n, const Prog* prog, const uint32_t* prio,
-                          uint32_t lane_max, uint32_t j1_max, uint32_t j4_max, uint32_t force_lane, uint32_t* blkcnt,
-                          uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
+                          uint32_t lane_max, uint32_t lite_max, uint32_t j1_max, uint32_t j4_max, uint32_t force_lane,
+                          uint32_t* blkcnt, uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
                           const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
                           uint32_t skip_min, uint32_t* nmark, hipStream_t st) {
     const uint32_t nblk = (mb + 255) / 256;
     if (!nblk) return hipSuccess;
-    hipLaunchKernelGGL(k_seg_bin, dim3(nblk), dim3(256), 0, st, segs, mp, n, prog, prio, lane_max, j1_max, j4_max, force_lane,
+    hipLaunchKernelGGL(k_seg_bin, dim3(nblk), dim3(256), 0, st, segs, mp, n, prog, prio, lane_max, lite_max, j1_max, j4_max,
+                       force_lane,
                        blkcnt, nblk, pq_ok, pq_wide, aux, ashort, along, amulti, mixc, mix, mix_cap, mixlen, mix_wide,
                        head_min, hot_tab, nhot, nhotseg, need_hot, need_blk, bmax, skip_min, nmark);
     return hipGetLastError();

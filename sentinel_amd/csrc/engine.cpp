@@ -93,8 +93,8 @@ hipError_t launch_seg(const uint32_t* keys, uint64_t n, uint32_t* flag, uint32_t
                       hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
                       uint32_t* part, uint32_t* nseg);
 hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n, const Prog* prog, const uint32_t* prio,
-                          uint32_t lane_max, uint32_t j1_max, uint32_t j4_max, uint32_t force_lane, uint32_t* blkcnt,
-                          uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
+                          uint32_t lane_max, uint32_t lite_max, uint32_t j1_max, uint32_t j4_max, uint32_t force_lane,
+                          uint32_t* blkcnt, uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
                           const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
@@ -711,6 +711,13 @@ struct sg_engine {
     int j1_stream = -1;     // SG_J1_STREAM=1 / 0: J1 after J16 / J8 on bin_stream[0] / after the lane bins (default:
                             // bin_stream[0] when the short aux nodes take the main stream, else the main stream)
     uint32_t lane_max = 256, j1_max = 4096, j4_max = 65536;
+    // k_lite's programs without param rules stay on a lane up to lite_max events (decide.hip k_seg_bin).  A full C4
+    // batch with 512 against 256: period 3.46 -> 3.37 ms (group 3.32 -> 3.06, decide 3.11 -> 3.12 ms); with 1,024
+    // k_lite's longest lanes are the decide stage's tail (4.42 ms).  512 for k_lane's programs too: C3 6.0 -> 9.0 ms
+    // a batch.  DESIGN.md §5 "The lane / J1 boundary".  With pinned bins lane_max holds for every lane bin, unless
+    // SG_LITE_MAX pins this one too
+    uint32_t lite_max = 512;
+    bool lite_pinned = false;
     uint32_t head_min = 0;       // SG_HEAD_MIN: single-rule THREAD / rate-limiter head segments longer than this leave
                                  // the lane bins for the event-driven head owner (0: the lane bins keep up to lane_max;
                                  // C3 A/B: 64 -> 1.15, 128 -> 1.27, 0 -> 1.27 G entries/s)
@@ -1479,6 +1486,10 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (const char* f = std::getenv("SG_PROF_BIN")) e->prof_bin = std::atoi(f);  // SG_DEBUG counters of J16/J4/J1
     // decide-bin thresholds (segment lengths); tuning knobs, the defaults are the measured best
     if (const char* v = std::getenv("SG_LANE_MAX")) { e->lane_max = (uint32_t)std::strtoul(v, nullptr, 0); e->bins_pinned = true; }
+    if (const char* v = std::getenv("SG_LITE_MAX")) {
+        e->lite_max = (uint32_t)std::strtoul(v, nullptr, 0);
+        e->lite_pinned = e->bins_pinned = true;
+    }
     if (const char* v = std::getenv("SG_J1_MAX")) { e->j1_max = (uint32_t)std::strtoul(v, nullptr, 0); e->bins_pinned = true; }
     if (const char* v = std::getenv("SG_HEAD_MIN")) e->head_min = (uint32_t)std::strtoul(v, nullptr, 0);
     if (const char* v = std::getenv("SG_J4_MAX")) { e->j4_max = (uint32_t)std::strtoul(v, nullptr, 0); e->bins_pinned = true; }
@@ -2741,6 +2752,12 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
         j1_max = std::min<uint32_t>(j1_max, 1024);
         j4_max = std::min<uint32_t>(j4_max, 4096);
     }
+    // k_lite's longer limit is a full batch's: a shard-sized batch and pinned bins keep one limit for every lane bin,
+    // and so does an engine with THREAD-grade / rate-limiter head programs (C3: the main stream, which the lane bins
+    // are on, is close behind its longest chain; 6.01 -> 6.36 ms a batch with the longer limit)
+    const uint32_t lite_max = e->lite_pinned ? e->lite_max
+                              : (e->bins_pinned || e->has_head || n < SHARD_BATCH) ? lane_max
+                                                                                   : std::max(lane_max, e->lite_max);
     // A cooperative owner's lanes sum a stretch's acquire units (<= 65,535 an event) in 32 bits before the 64-bit
     // reduction at the stretch's end, so one owner of 64 * NW lanes takes at most 65,000 events a lane: a pinned limit
     // above that hands the segment to the next wider owner.  (The 512-lane owner ends at J8_MAX = 2^23 events; the
@@ -2761,7 +2778,7 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
         if (e->has_mix) {  // the XF_MIX lists of this slot
             if (int mrc = ensure_mix(B, mb)) return mrc;
         }
-        HIPCHK(launch_seg_bin(e->d_segs, e->d_bsmall + 1, mb, n, e->d_prog, e->d_prio, lane_max, j1_max, j4_max,
+        HIPCHK(launch_seg_bin(e->d_segs, e->d_bsmall + 1, mb, n, e->d_prog, e->d_prio, lane_max, lite_max, j1_max, j4_max,
                               force_lane ? 1 : 0, e->d_blkcnt, e->pq_on ? 1u : 0u, e->pq_wide, ext ? e->d_bsmall + 130 : nullptr,
                               B.d_ashort, B.d_along, B.d_amulti, e->d_bsmall + 6, e->has_mix ? B.d_mix : nullptr,
                               (uint32_t)B.mix_cap, e->d_bsmall + 72, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
@@ -2867,7 +2884,8 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
     G.n = n; G.n_args = n_args; G.gbase = e->gbase; G.ring_mask = ring_mask;
     G.dev_ev = dev_ev; G.dev_ext = dev_ext; G.dev_args = dev_args;
     G.out = out; G.dev_out = dev_out; G.vin = vin;
-    G.epoch = e->epoch; G.skip_min = skip_min; G.lane_max = lane_max; G.mb = mb;
+    // (lane_max: the length up to which every segment is a lane one, for the decide stage's aux_early)
+    G.epoch = e->epoch; G.skip_min = skip_min; G.lane_max = std::min(lane_max, lite_max); G.mb = mb;
     G.ext = ext != nullptr; G.host_out = host_out; G.force_lane = force_lane;
     G.set = (int)(e->seq % sg_engine::N_SETS);
     e->grouped = k;
