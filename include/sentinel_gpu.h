@@ -190,7 +190,11 @@ enum {
                                    instead of sg_load_authority_rules).  Those slots sit between ParamFlowSlot and
                                    FlowSlot (param/slots/HotParamSlotChainBuilder.java:39-50), so the param checks still
                                    run (and may block first); otherwise the entry is blocked with SG_BLOCK_UPSTREAM --
-                                   before the engine's own authority check, as SystemSlot precedes AuthoritySlot -- and
+                                   before the engine's own authority check, as SystemSlot precedes AuthoritySlot.  The
+                                   resource keeps its cooperative owner (the entry is a block whose word is written
+                                   ahead of it); only short segments, resources whose rules are param rules alone, read
+                                   an origin / context node or name a RELATE resource, and resources that also saw a
+                                   prioritized or NullContext entry are decided one lane per resource from then on -- and
                                    StatisticSlot counts the block (StatisticSlot.java:97-117) */
 };
 /* EXIT/TRACE aux: low 48 bits = global index of the ENTRY event this refers
@@ -362,7 +366,9 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
  * AuthorityRuleChecker.passCheck (AuthorityRuleChecker.java:30-65) on the origin of the entry's sg_event_ext: the
  * empty origin passes; otherwise BLACK blocks an origin that equals one of limit_app.split(","), WHITE one that
  * equals none.  It runs where AuthoritySlot sits: after the entry's param rules and after SG_F_BLOCKED_UPSTREAM,
- * before the first flow rule; a blocked entry is SG_BLOCK_AUTHORITY and is counted as any blocked entry.  Loading
+ * before the first flow rule; a blocked entry is SG_BLOCK_AUTHORITY and is counted as any blocked entry.  A resource
+ * with blocked entries keeps its cooperative owner, as with SG_F_BLOCKED_UPSTREAM (what stays on a lane: see there;
+ * also an origin id >= 2^20).  Loading
  * interns no origin: a listed name takes effect once sg_intern_origin has given it an id. */
 int sg_load_authority_rules(sg_engine* e, const sg_authority_rule* rules, uint32_t n, uint32_t* n_loaded);
 

@@ -128,7 +128,7 @@ __device__ __forceinline__ void lacc_commit(const DevState& S, int32_t max_rt, u
 // the merge is associative, so a node may be committed in several parts)
 __device__ void aux_walk(const SEv* __restrict__ recs, const uint32_t* __restrict__ dec, const DevState& S,
                          int32_t max_rt, uint32_t res, bool chain, uint32_t a, uint32_t b, int64_t t0, uint32_t* bflags) {
-    const int64_t b500 = t0 / 500, b1000 = t0 / 1000;
+    const int64_t b500 = (t0 / 500) & ~1ll, b1000 = (t0 / 1000) & ~1ll;  // (even: a relative index keeps the window's parity)
     LAcc c[AUX_K];
 #pragma unroll
     for (int k = 0; k < AUX_K; ++k) lacc_zero(c[k], AUX_EMPTY32);
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void k_aux_cold(const SEv* __restrict__ recs, 
     __shared__ uint32_t gstart[AUX_G], gres[AUX_G], gpre[AUX_G + 1], gchain[AUX_G];
     __shared__ uint32_t claims;
     const uint32_t m = *cnt;
-    const int64_t b500 = t0 / 500, b1000 = t0 / 1000;
+    const int64_t b500 = (t0 / 500) & ~1ll, b1000 = (t0 / 1000) & ~1ll;  // (even: a relative index keeps the window's parity)
     tab_clear(T);
     if (threadIdx.x == 0) claims = 0;
     for (uint32_t g0 = blockIdx.x * AUX_G; g0 < m; g0 += gridDim.x * AUX_G) {
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256) void k_aux_piece(const SEv* __restrict__ recs,
     __shared__ Tab T;
     __shared__ uint32_t off, claims;
     const uint32_t m = *cnt;
-    const int64_t b500 = t0 / 500, b1000 = t0 / 1000;
+    const int64_t b500 = (t0 / 500) & ~1ll, b1000 = (t0 / 1000) & ~1ll;  // (even: a relative index keeps the window's parity)
     tab_clear(T);
     if (threadIdx.x == 0) claims = 0;
     for (uint32_t k = blockIdx.x; k < m; k += gridDim.x) {

@@ -172,7 +172,8 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
                                                  const uint16_t* __restrict__ hot_tab, uint32_t nhot,
                                                  const uint32_t* __restrict__ nhotseg, uint32_t* __restrict__ need_hot,
                                                  uint32_t* __restrict__ need_blk, const uint32_t* __restrict__ bmax,
-                                                 uint32_t skip_min, uint32_t* __restrict__ nmark) {
+                                                 uint32_t skip_min, uint32_t* __restrict__ nmark,
+                                                 uint32_t* __restrict__ ubc) {
     __shared__ uint32_t cnt[N_BINS];
     for (uint32_t b = threadIdx.x; b < N_BINS; b += blockDim.x) cnt[b] = 0;
     __syncthreads();
@@ -191,23 +192,31 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
         const uint32_t pm = prio[sg.res];
         // decided one lane per segment whatever the length: a live borrow ring (PM_PRIO), events only k_lane takes
         // (PM_LANE), origin / context nodes the rules read (PX_ORIGIN / PX_CHAIN: k_lane<16> keeps them inline)
-        const bool lane_only = (pm & (PM_PRIO | PM_LANE)) != 0 || ((pm & PM_AUX) && (p.multi & (PX_ORIGIN | PX_CHAIN)));
-        const bool inline_aux = (pm & PM_AUX) && (lane_only || p.multi);  // k_lane<16> updates the nodes itself
-        const int nr = p.multi ? 16 : p.n_param + p.n_flow + p.n_degrade;  // PX_*: decided with 16-rule lanes
+        const bool lane_base = (pm & (PM_PRIO | PM_LANE)) != 0 || ((pm & PM_AUX) && (p.multi & (PX_ORIGIN | PX_CHAIN)));
         // XF_MIX: the param checks run in k_pq's pre pass (args[0] from the key ring: no argument lists)
         const bool mixp = (p.xf & XF_MIX) && pq && mix && !(pm & PM_ARGL);
+        // A resource that has seen a pre-blocked ENTRY (PM_UBLK; its records carry RF_UBLK): the cooperative owners take
+        // its segment where they would take it without the mark -- by the lane bins' own limit, not k_lite's longer one
+        // nor the head owner's shorter one: neither kernel is taught the class -- with the pre-blocked ENTRYs as blocks
+        // whose words k_ublk_words writes (SEG_UBLK).  Everything else with the mark keeps the lane bins (lane_entry).
+        const bool ub = (pm & PM_UBLK) != 0;
+        const bool ubs = ub && !lane_base && !force_lane && !(p.pflags & PF_SERIAL) && (p.n_param == 0 || mixp) &&
+                         !p.multi && sg.len > lane_max;
+        const bool lane_only = lane_base || (ub && !ubs);
+        const bool inline_aux = (pm & PM_AUX) && (lane_only || p.multi);  // k_lane<16> updates the nodes itself
+        const int nr = p.multi ? 16 : p.n_param + p.n_flow + p.n_degrade;  // PX_*: decided with 16-rule lanes
         // k_lite: no param rules, <= 2 DefaultController flow stages (QPS or thread), <= 2 breakers
         // (or one QPS DefaultController param rule on args[0] before them, scalar args: k_lite<true>), every
         // flow stage on the ClusterNode (PF_SERIAL: a rule of another strategy, e.g. one whose node is never
         // selected, FlowRuleChecker.selectReferenceNode, is k_lane's)
-        const bool lite = (p.n_param == 0 || ((p.xf & XF_PLITE) && !(pm & PM_ARGL))) && !p.multi && !lane_only &&
+        const bool lite = (p.n_param == 0 || ((p.xf & XF_PLITE) && !(pm & PM_ARGL))) && !p.multi && !lane_only && !ub &&
                           (p.pflags & PF_J16) && !(p.pflags & (PF_WARM | PF_SERIAL));
         // the lane bins keep a segment up to lane_max events; k_lite's programs without param rules up to lite_max
         // (a full batch: 512 against 256, engine.cpp lite_max -- measured on C4 and C2; k_lane's programs keep
         // lane_max: C3 with 512 for every program 6.0 -> 9.0 ms a batch)
         const uint32_t lmax = (lite && p.n_param == 0) ? lite_max : lane_max;
         // single-rule THREAD-grade / rate-limiter heads (head.hip k_head) leave the lane bins from head_min events on
-        const uint32_t cmin = (head_min && (p.xf & (XF_HEADT | XF_HEADR)) && head_min < lmax) ? head_min : lmax;
+        const uint32_t cmin = (head_min && !ub && (p.xf & (XF_HEADT | XF_HEADR)) && head_min < lmax) ? head_min : lmax;
         const bool coop = !force_lane && !(p.pflags & PF_SERIAL) && (p.n_param == 0 || mixp) && sg.len > cmin &&
                           !lane_only && !p.multi;
         if (coop && p.n_param) mixk = sg.len > mix_wide ? 2u : 1u;  // (wide: pvalue.hip's passes, where on)
@@ -268,8 +277,10 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
                 tabs = true;
             }
         }
+        // (ubs implies coop, and not PF_PQ -- param rules without XF_MIX: one of J1 / J4 / J8 / J16)
+        if (ub && ubc) atomicAdd(&ubc[ubs ? 0 : 1], 1u);  // (diagnostics and the host's launch of k_ublk_words)
         const uint32_t rank = atomicAdd(&cnt[bin], 1u);
-        sg.bin = bin | (auxp ? SEG_AUXP : 0u) | (tabs ? SEG_TABS : 0u) | (rank << SEG_RANK_SHIFT);
+        sg.bin = bin | (auxp ? SEG_AUXP : 0u) | (tabs ? SEG_TABS : 0u) | (ubs ? SEG_UBLK : 0u) | (rank << SEG_RANK_SHIFT);
         segs[s] = sg;
     }
     if (aux) {  // (wave-uniform: every lane of the wave takes part)
@@ -298,7 +309,7 @@ __global__ __launch_bounds__(256) void k_seg_order(Seg* __restrict__ segs, const
     if (s >= *mp) return;
     const uint32_t v = segs[s].bin, bin = v & 0x3F;
     order[off[(uint64_t)bin * nblk + blockIdx.x] + (v >> SEG_RANK_SHIFT)] = s;
-    segs[s].bin = v & ((1u << SEG_RANK_SHIFT) - 1);  // the bin | SEG_AUXP | SEG_TABS
+    segs[s].bin = v & ((1u << SEG_RANK_SHIFT) - 1);  // the bin | SEG_AUXP | SEG_TABS | SEG_UBLK
 }
 // per-bin first offsets (+ total) for the host: out[b] = off[b][0], out[N_BINS] = m
 __global__ void k_bin_offsets(const uint32_t* __restrict__ off, uint32_t nblk, const uint32_t* __restrict__ mp,
@@ -491,7 +502,7 @@ __global__ __launch_bounds__(256) void k_fill(const Span* __restrict__ spans, co
             const uint4 r = reinterpret_cast<const uint4*>(recs)[p];
             uint32_t d = mk_dec(ST_NOT_ENTRY, 0, 0);
             if ((r.w & 0xFFu) == SG_EV_ENTRY) {
-                if ((r.w >> 8) & RF_PBLK) continue;  // the param pre pass's verdict stands
+                if ((r.w >> 8) & RF_PBLK) continue;  // the param pre pass's / k_ublk_words's verdict stands
                 const double curv = (double)j_iadd(sp.pint, (int)(r.z & 0xFFFFu));
                 uint32_t v = 0;
 #pragma unroll
@@ -502,6 +513,34 @@ __global__ __launch_bounds__(256) void k_fill(const Span* __restrict__ spans, co
             dec[p] = d;
         }
     }
+}
+
+// The words of the pre-blocked ENTRYs (RF_UBLK) of the SEG_UBLK segments, between the param pre pass and the owners of
+// the batch: SystemSlot's block (the record kept SG_F_BLOCKED_UPSTREAM) wins over the authority rule's, as in
+// lane_entry; rule slot 0, wait 0.  An XF_MIX segment's pre pass has checked such an ENTRY like any other (it knows
+// nothing of the flag) and taken its tokens; where a param rule blocked it (RF_PBLK) that word stands: ParamFlowSlot
+// sits before both slots.  Every other one gets its word and RF_PBLK here, the class the owners know: they count the
+// ENTRY as a block and store nothing for it.  (Testing RF_PBLK | RF_UBLK in k_jac instead spilled 1 .. 3 more VGPRs in
+// the 1024- and 256-lane owners; with one bit their code is the parent's.)  The post passes read the words, not the
+// flag.  One workgroup per segment of the cooperative bins' dispatch list (order[0 .. m)); a segment without the flag
+// is left at once.  cnt: the words written (diagnostics).
+__global__ __launch_bounds__(256) void k_ublk_words(SEv* __restrict__ recs, const Seg* __restrict__ segs,
+                                                    const uint32_t* __restrict__ order, uint32_t m,
+                                                    uint32_t* __restrict__ dec, uint32_t* __restrict__ cnt) {
+    if (blockIdx.x >= m) return;
+    const Seg sg = segs[order[blockIdx.x]];
+    if (!(sg.bin & SEG_UBLK)) return;
+    uint32_t nw = 0;
+    for (uint32_t p = threadIdx.x; p < sg.len; p += blockDim.x) {
+        const uint32_t w = reinterpret_cast<const uint4*>(recs)[sg.start + p].w;
+        const uint32_t fl = (w >> 8) & 0xFFu;
+        if ((w & 0xFFu) == SG_EV_ENTRY && (fl & RF_UBLK) && !(fl & RF_PBLK)) {
+            recs[sg.start + p].flags = (uint8_t)(fl | RF_PBLK);
+            dec[sg.start + p] = mk_dec((fl & SG_F_BLOCKED_UPSTREAM) ? ST_BLOCK_UPSTREAM : ST_BLOCK_AUTHORITY, 0, 0);
+            ++nw;
+        }
+    }
+    if (nw) atomicAdd(cnt, nw);
 }
 
 // CtSph.lookProcessChain (core/CtSph.java:206-227): resources touched by this batch with neither a
@@ -1002,7 +1041,8 @@ __device__ int aux_check(const DevState& S, const DevCfg& cfg, const DRule& r, R
 
 // AuthoritySlot.checkBlackWhiteAuthority (core/slots/block/authority/AuthoritySlot.java:48-65): the resource's
 // authority rule blocks an entry from this origin.  Reads the table only when rules are loaded and the entry
-// names an origin; the intake sites (k_rs_first, k_grp_first, k_tiny) mark a resource PM_LANE with the same test.
+// names an origin; the intake sites (k_rs_first, k_grp_first / k_grp_records, k_tiny) mark a resource PM_UBLK (SG_UBLK=0:
+// PM_LANE) and the record RF_UBLK with the same test.
 __device__ __forceinline__ bool authority_blocks(const DevState& S, uint32_t res, uint32_t origin_id) {
     return S.auth != nullptr && origin_id != 0 && auth_blocks(S.auth, S.auth_ids, res, origin_id);
 }
@@ -1995,7 +2035,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
     const uint32_t res = sg.res;
     const Prog pg = S.prog[res];
     if (CLS != 0 && (((pg.pflags & PF_FROZEN) != 0) != (CLS == 1))) return;  // the other instantiation's segment
-    if ((NW == 16 || NW == 4 || NW == 1) && (pg.xf & (XF_HEADT | XF_HEADR)) && !(cfg.dbg_flags & HEAD_OFF)) return;  // k_head's
+    if ((NW == 16 || NW == 4 || NW == 1) && (pg.xf & (XF_HEADT | XF_HEADR)) && !(cfg.dbg_flags & HEAD_OFF) &&
+        !(sg.bin & SEG_UBLK))
+        return;  // k_head's (which leaves a segment with pre-blocked ENTRYs here)
     const int nf = pg.n_flow, nd = pg.n_degrade, nr = nf + nd;
     // the minute window in LDS (sh.minl): loaded here, written back at the segment's end; no other kernel of the
     // decide stage touches this resource's minute buckets while its owner runs
@@ -2006,7 +2048,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
     // XF_MIX: the param rules come first in the program and k_pq's pre pass has decided them: an ENTRY one of them
     // blocked carries RF_PBLK (its dec[] word is final) and is a block here, nothing more
     const uint32_t roff = pg.rule_off + pg.n_param;
-    const bool mixp = pg.n_param != 0;
+    // SEG_UBLK: so does an ENTRY SystemSlot or the authority rule blocked (RF_UBLK): k_ublk_words wrote its word and
+    // raised RF_PBLK on it, so every test of the class below stays the one-bit test it was
+    const bool mixp = pg.n_param != 0 || (sg.bin & SEG_UBLK) != 0;
     if (tid == 0) {
         node_load(sh.node, S, res);
         sh.round_open = 0;
@@ -2476,7 +2520,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                                 if (s < nf && (((warmm >> s) & 1) ? !(curw <= fcount[s]) : curv > fcount[s])) fd = fdec[s];
                         }
                         if (fd == 0 && cutk0) fd = cdec;
-                        if ((rr[k].w >> 8) & RF_PBLK) fd = 1u;  // blocked by a param rule: its word is written
+                        if ((rr[k].w >> 8) & RF_PBLK) fd = 1u;  // blocked by a param rule (or pre-blocked): its word is written
                         fdv[k] = fd;
                         const bool stop = q < sg.len && (!in || (ek == SG_EV_ENTRY && fd == 0));
                         if (stop && q < mystop) mystop = q;
@@ -3129,7 +3173,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
                                 if (s < nf && (((warmm >> s) & 1) ? !(fzd + (double)ec <= fl[s]) : curv > fl[s])) bs = (uint32_t)s;
                             uint32_t fd = bs < (uint32_t)nf ? mk_dec(ST_BLOCK_FLOW, sh.rules[bs].slot, 0)
                                                             : (fcut ? mk_dec(ST_BLOCK_DEGRADE, sh.rules[nf].slot, 0) : 0u);
-                            if ((rr[k].w >> 8) & RF_PBLK) fd = 1u;  // blocked by a param rule: its word is written
+                            if ((rr[k].w >> 8) & RF_PBLK) fd = 1u;  // blocked by a param rule (or pre-blocked): its word is written
                             fdv[k] = fd;
                             fbs[k] = bs;
                             const bool stop = act && (!in || (ek == SG_EV_ENTRY && fd == 0));
@@ -3938,13 +3982,13 @@ __global__ __launch_bounds__(TINY_MAX) void k_tiny(const sg_event* __restrict__ 
                 if (x.origin_id >> TAG_ORIGIN_BITS) mark |= PM_LANE;
             }
             if (e.kind == SG_EV_ENTRY && e.res_id < max_res && authority_blocks(S, e.res_id, x.origin_id))
-                mark |= PM_LANE;  // (as k_rs_first)
+                mark |= (cfg.dbg_flags & UBLK_OFF) ? PM_LANE : PM_UBLK;  // (as k_rs_first)
         }
         if (own_args && e.kind == SG_EV_EXIT && (e.flags & SG_F_EXIT_ARGS)) mark |= PM_XARGS;
         if (e.kind == SG_EV_ENTRY) {
             if (S.key_ring) S.key_ring[(gbase + t) & ring_mask] = key0;
             if (e.flags & SG_F_PRIORITIZED) mark |= PM_PRIO;
-            if (e.flags & SG_F_BLOCKED_UPSTREAM) mark |= PM_LANE;
+            if (e.flags & SG_F_BLOCKED_UPSTREAM) mark |= (cfg.dbg_flags & UBLK_OFF) ? PM_LANE : PM_UBLK;
         } else {
             if (e.kind == SG_EV_EXIT && own_args && S.key_ring) S.key_ring[(gbase + t) & ring_mask] = key0;
             const uint64_t ref = e.aux & SG_REF_NONE;
@@ -3980,7 +4024,7 @@ __global__ __launch_bounds__(TINY_MAX) void k_tiny(const sg_event* __restrict__ 
         r.cnt = e.count;
         r.rt = 0;
         r.kind = e.kind;
-        r.flags = (uint8_t)(e.flags & 0x3Fu);
+        r.flags = (uint8_t)(e.flags & 0x1Fu);  // (no RF_UBLK: lane_entry decides every segment here)
         r.code = RC_NONE;
         r.pad = 0;
         uint32_t tag = 0;
@@ -4149,13 +4193,13 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
                           const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
-                          uint32_t skip_min, uint32_t* nmark, hipStream_t st) {
+                          uint32_t skip_min, uint32_t* nmark, uint32_t* ubc, hipStream_t st) {
     const uint32_t nblk = (mb + 255) / 256;
     if (!nblk) return hipSuccess;
     hipLaunchKernelGGL(k_seg_bin, dim3(nblk), dim3(256), 0, st, segs, mp, n, prog, prio, lane_max, lite_max, j1_max, j4_max,
                        force_lane,
                        blkcnt, nblk, pq_ok, pq_wide, aux, ashort, along, amulti, mixc, mix, mix_cap, mixlen, mix_wide,
-                       head_min, hot_tab, nhot, nhotseg, need_hot, need_blk, bmax, skip_min, nmark);
+                       head_min, hot_tab, nhot, nhotseg, need_hot, need_blk, bmax, skip_min, nmark, ubc);
     return hipGetLastError();
 }
 // off = exclusive scan of blkcnt (bin-major); writes the per-bin offsets to bin_off[0..N_BINS]
@@ -4181,6 +4225,13 @@ hipError_t launch_gather(const SEv* rec_o, const uint32_t* vals, const uint32_t*
 hipError_t launch_fill(const Span* spans, const uint32_t* nspan, uint32_t cap, const SEv* recs, const Prog* prog,
                        const DRule* rules, uint32_t* dec, hipStream_t st) {
     hipLaunchKernelGGL(k_fill, dim3(2048), dim3(256), 0, st, spans, nspan, cap, recs, prog, rules, dec);
+    return hipGetLastError();
+}
+// order[0 .. m): the dispatch list of the cooperative bins (BIN_J16 .. BIN_J8, contiguous)
+hipError_t launch_ublk_words(SEv* recs, const Seg* segs, const uint32_t* order, uint32_t m, uint32_t* dec,
+                             uint32_t* cnt, hipStream_t st) {
+    if (!m) return hipSuccess;
+    hipLaunchKernelGGL(k_ublk_words, dim3(m), dim3(256), 0, st, recs, segs, order, m, dec, cnt);
     return hipGetLastError();
 }
 hipError_t launch_resolve(const uint32_t* prev, uint32_t np, const uint8_t* ring, SEv* recs, const uint32_t* vals,

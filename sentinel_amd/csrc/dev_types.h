@@ -52,15 +52,20 @@ __host__ __device__ inline uint32_t ni_tm(uint32_t idx) { return 1u << (NI_TM_SH
 // segments to the per-lane kernel
 enum : uint8_t {
     PM_PRIO = 1,         // a prioritized ENTRY was seen: the second window's borrow ring is live
-    PM_LANE = 2,         // an event only k_lane implements was seen: SG_F_BLOCKED_UPSTREAM, an ENTRY its authority
-                         // rule blocks, a NullContext, an origin id >= 2^20 (not packable into the record's node tag)
+    PM_LANE = 2,         // an event only k_lane implements was seen: a NullContext, an origin id >= 2^20 (not packable
+                         // into the record's node tag); with SG_UBLK=0 also every pre-blocked ENTRY (PM_UBLK)
     PM_AUX = 4,          // an event carried an origin or a named context: the resource keeps its origin
                          // StatisticNodes / context DefaultNodes whatever its rules are.  Rules that read them
                          // (PX_ORIGIN / PX_CHAIN) decide on k_lane<16>; otherwise the segment decides on its usual
                          // owner and aux.hip updates the nodes from the committed verdicts afterwards
     PM_ARGL = 8,         // an event's argument was a Collection / array (per-element checks: not k_pq's; its maps
                          // are grown to full size)
-    PM_XARGS = 16        // an EXIT released thread counts with args of its own (sg_submit_ex)
+    PM_XARGS = 16,       // an EXIT released thread counts with args of its own (sg_submit_ex)
+    PM_UBLK = 32         // a pre-blocked ENTRY was seen: SG_F_BLOCKED_UPSTREAM, or an ENTRY its authority rule blocks.
+                         // Its record carries RF_UBLK.  The cooperative owners (k_jac, k_fill) take such a segment
+                         // (SEG_UBLK) with the pre-blocked ENTRYs as blocks whose words k_ublk_words writes; what they
+                         // do not take -- short segments (k_lite is not taught the class), PF_PQ, PF_SERIAL, RELATE
+                         // components, origin / CHAIN rules, prioritized or PM_LANE resources -- keeps the lane bins
 };
 // SEv.x of an ENTRY (and of an EXIT / TRACE that names no ENTRY of this batch) in an sg_submit_ex batch: the
 // origin / context node tag of the event, origin id | context id << 20 (0: no origin, default context)
@@ -71,6 +76,11 @@ __host__ __device__ inline uint32_t tag_ctx(uint32_t tag) { return tag >> TAG_OR
 #define RF_OWN_ARGS 0x80u  // EXIT of sg_submit_ex with its own args: its args[0] key is in the key ring at its index
 #define RF_PBLK 0x40u      // ENTRY of an XF_MIX segment that a param rule blocked (param.hip k_pq pre pass): its dec[]
                            // word is final; the flow / degrade owner counts it as a block and evaluates nothing
+#define RF_UBLK 0x20u      // ENTRY blocked before FlowSlot by SystemSlot (with SG_F_BLOCKED_UPSTREAM: status 6) or by its
+                           // resource's authority rule (without: status 7), set at intake (a bit the ABI leaves unused
+                           // and the intake masks off the caller's flags).  In a SEG_UBLK segment k_ublk_words, after the
+                           // param pre pass (a param rule's block comes first and stands), writes its word and raises
+                           // RF_PBLK on it: the owner's class.  A lane owner ignores the bit (lane_entry decides)
 
 struct NodeInfo {
     int32_t thread;      // StatisticNode.curThreadNum
@@ -235,6 +245,8 @@ enum : uint8_t { ST_PASS = 0, ST_PASS_WAIT = 1, ST_BLOCK_FLOW = 2, ST_BLOCK_DEGR
 #define TABLES_ALL 32768u  // SG_DEBUG_FLAGS: the hot / cold group stage builds the side tables for every position (A/B)
 #define LITE_CHECK 65536u  // DevCfg.dbg_flags (SG_LITE_CHECK=1): k_lite reads the window start of every minute bucket it
                            // stores without a load and raises BF_LITE_STALE if the bucket was not stale
+#define UBLK_OFF 131072u  // DevCfg.dbg_flags (SG_UBLK=0): a pre-blocked ENTRY marks PM_LANE and its record carries no
+                          // RF_UBLK: every such resource on a lane, as before the cooperative owners took the class (A/B)
 struct DevCfg {
     int32_t max_rt;
     int32_t occupy_timeout;
@@ -258,9 +270,11 @@ struct Seg {
 #define SEG_PV 0x40u    // Seg.bin: pvalue.hip decided the segment's param checks (k_pq's pre pass leaves it)
 #define SEG_PVT 0x100u  // Seg.bin: pvalue.hip's post pass updated the thread-count map (k_pq's post pass leaves it)
 #define SEG_TABS 0x200u  // Seg.bin: the segment's side tables (forward links, bst[]) exist: its owner may skip frozen
-                         // stretches (k_seg_bin; bits 0..5 the bin, 6..9 these flags, the rank inside its block above
+                         // stretches (k_seg_bin; bits 0..5 the bin, 6..10 these flags, the rank inside its block above
                          // them until k_seg_order places the segment)
-#define SEG_RANK_SHIFT 10
+#define SEG_UBLK 0x400u  // Seg.bin: a PM_UBLK resource's segment on a cooperative owner: RF_UBLK ENTRYs are pre-decided
+                         // blocks (k_head leaves it to k_jac; bits 6..10 the flags)
+#define SEG_RANK_SHIFT 11
 
 // pvalue.hip: the value-parallel pre pass of long XF_MIX segments
 // per listed segment (the wide XF_MIX list): what the pre pass found

@@ -35,7 +35,7 @@ hipError_t launch_rs_first(const sg_event* ev, uint64_t n, uint32_t max_res, uin
                            uint32_t* ghist, uint32_t nblocks, uint32_t* bflags, int64_t* t0_out, uint32_t* prio,
                            uint64_t* key_ring, const uint32_t* comp, const sg_event_ext* ext, const sg_arg* args,
                            uint64_t n_args, uint32_t max_ctx, const AuthDesc* auth, const uint32_t* auth_ids,
-                           hipStream_t st);
+                           uint32_t ublk, hipStream_t st);
 // db = digit bits (8 or 10)
 hipError_t launch_radix_hist(const uint32_t* keys, uint64_t n, int shift, uint32_t* ghist, uint32_t nblocks,
                              hipStream_t st);
@@ -52,7 +52,7 @@ hipError_t launch_grp_first(const sg_event* ev, uint64_t n, uint32_t max_res, ui
                             const AuthDesc* auth, const uint32_t* auth_ids,
                             const uint16_t* hot_tab, uint32_t nhot, uint32_t nblocks, uint32_t* words,
                             uint32_t* hot_hist, uint32_t* ckeys, uint32_t* cvals, uint32_t* ccnt, uint32_t* chist,
-                            hipStream_t st);
+                            uint32_t ublk, hipStream_t st);
 hipError_t launch_hot_scan(uint32_t* C, uint32_t nblocks, uint32_t nhot, uint32_t* part, uint32_t* hb, uint32_t* total,
                            hipStream_t st);
 hipError_t launch_hot_bmax(const sg_event* ev, uint32_t nblocks, const uint32_t* P, uint32_t nhot, const uint32_t* hb,
@@ -62,7 +62,8 @@ hipError_t launch_grp_records(const sg_event* ev, uint64_t n, uint64_t gbase, ui
                               const uint32_t* hb, SEv* recs, uint32_t* svals, uint32_t* prev,
                               uint32_t* nprev, uint32_t* bst, uint32_t* bflags, const sg_event_ext* ext,
                               const sg_arg* args, uint32_t max_ctx, Link* link, uint32_t epoch,
-                              const uint32_t* need_hot, const uint32_t* need_blk, hipStream_t st);
+                              const uint32_t* need_hot, const uint32_t* need_blk, uint32_t max_res,
+                              const AuthDesc* auth, const uint32_t* auth_ids, uint32_t ublk, hipStream_t st);
 hipError_t launch_hot_segs(const uint32_t* hb, uint32_t nhot, const uint32_t* hot_list, Seg* segs, uint32_t* out,
                            hipStream_t st);
 hipError_t launch_hot_build(const Seg* segs, const uint32_t* mp, uint32_t mb, uint32_t min_len, uint32_t max_res, uint16_t* hot_tab,
@@ -98,7 +99,7 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
                           const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
-                          uint32_t skip_min, uint32_t* nmark, hipStream_t st);
+                          uint32_t skip_min, uint32_t* nmark, uint32_t* ubc, hipStream_t st);
 // aux.hip
 hipError_t launch_aux(const SEv* recs, const Seg* segs, const uint32_t* aux, const uint32_t* ashort,
                       const uint64_t* along, uint64_t* apiece, const uint64_t* amulti, const DevState& S, const DevCfg& cfg,
@@ -155,6 +156,8 @@ hipError_t launch_fill(const Span* spans, const uint32_t* nspan, uint32_t cap, c
                        const DRule* rules, uint32_t* dec, hipStream_t st);
 hipError_t launch_resolve(const uint32_t* prev, uint32_t np, const uint8_t* ring, SEv* recs, const uint32_t* vals,
                           const sg_event_ext* ext, hipStream_t st);
+hipError_t launch_ublk_words(SEv* recs, const Seg* segs, const uint32_t* order, uint32_t m, uint32_t* dec,
+                             uint32_t* cnt, hipStream_t st);
 hipError_t launch_post_w(const uint32_t* words, const uint32_t* P, uint32_t nhot, const uint32_t* dec, uint64_t n,
                          uint64_t gbase, uint8_t* ring, uint64_t ring_mask, uint32_t* out, hipStream_t st);
 hipError_t launch_post(const uint32_t* pos_of, const uint32_t* dec, uint64_t n, uint64_t gbase, uint8_t* ring,
@@ -577,6 +580,7 @@ struct sg_engine {
         bool radix = false;            // this batch took the radix group stage (d_posof), else the hot / cold one
         uint32_t nhot = 0;             // ... with these hot ids (its words and P in d_flag / d_pos)
         uint32_t hot_marked = 0;       // ... of which k_seg_bin marked this many for the side tables (d_bsmall[73])
+        uint32_t ublk_coop = 0, ublk_lane = 0;  // PM_UBLK segments in cooperative / lane bins (d_bsmall[74], [75])
         Seg* d_segs = nullptr;
         uint64_t* d_cand = nullptr;
         uint32_t* d_bsmall = nullptr;  // [0] bflags [1] nseg [2] ncand [3] nprev [4..5] t0 [8..8+N_BINS] bin offsets
@@ -623,7 +627,7 @@ struct sg_engine {
     hipEvent_t evset[N_SETS][5] = {};
     uint32_t* h_mirror = nullptr;  // pinned, N_SETS x MIRROR_WORDS: d_bsmall[0..121) as the decide stage left it
     uint64_t seq = 0;              // batches handed to the decide stage so far (batch i has set i % N_SETS)
-    struct InFlight { int set; uint32_t hot_marked; };
+    struct InFlight { int set; uint32_t hot_marked, ublk_coop, ublk_lane; };
     std::deque<InFlight> inflight;  // handed off, not yet collected (timings, flags), oldest first
     hipStream_t gstream = nullptr;
     std::vector<std::array<double, 4>> tlog;  // per batch [group, decide, post, total] ms, by collect()
@@ -644,6 +648,7 @@ struct sg_engine {
     uint64_t need_words = 0;
     uint32_t* d_edges = nullptr;
     uint32_t hot_marked_last = 0;  // hot ids marked for the side tables in the last collected batch (sgx_hot_marked)
+    uint32_t ublk_last[3] = {0, 0, 0};  // sgx_preblocked_last: PM_UBLK segments in cooperative / lane bins, RF_UBLK words
     bool radix_group = false;    // SG_DEBUG_FLAGS & 8192: the all-radix group stage (A/B)
     uint64_t radix_below = 1u << 18;  // SG_RADIX_BELOW: batches of fewer events take the radix group stage (the drop-in's
                                       // 65,536-event batches: 36 vs 30-32 M entries/s on the hot / cold one)
@@ -903,7 +908,8 @@ int ensure_batch(sg_engine* e, uint64_t n) {
 }
 
 constexpr uint32_t HEAD_WORDS = 77;     // d_bsmall words the host reads after the group stage
-constexpr uint32_t MIRROR_WORDS = 121;  // ... and after the decide stage ([0] bflags, [120] frozen spans)
+constexpr uint32_t MIRROR_WORDS = 121;  // ... and after the decide stage ([0] bflags, [119] RF_UBLK words written,
+                                        // [120] frozen spans)
 
 // The oldest batch in flight: wait for its decide stage, record its stage times and the idle time of both streams
 // before it, and check its device flags (from the pinned mirror its decide stage filled: nothing is enqueued here).
@@ -938,6 +944,9 @@ static int collect(sg_engine* e) {
     const uint32_t bflags = mir[0];
     e->spans_total += mir[120];
     e->hot_marked_last = f.hot_marked;
+    e->ublk_last[0] = f.ublk_coop;
+    e->ublk_last[1] = f.ublk_lane;
+    e->ublk_last[2] = mir[119];
     // Flags the decide kernels raise (the group stage's own checks return before the decide stage runs):
     // an EXIT/TRACE whose reference names an event that is not an earlier ENTRY of its resource, and a
     // batch starting before the last window a resource already holds (the clock went back).
@@ -1497,6 +1506,9 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     if (const char* v = std::getenv("SG_HANDOFF")) e->handoff_late = v[0] != '0';
     if (const char* v = std::getenv("SG_TINY")) e->tiny_on = v[0] != '0';
     if (const char* v = std::getenv("SG_LITE_CHECK")) { if (v[0] == '1') e->dbg_flags |= LITE_CHECK; }
+    // SG_UBLK=0: pre-blocked ENTRYs (SG_F_BLOCKED_UPSTREAM, authority blocks) send their resource to a lane (A/B)
+    e->dbg_flags &= ~UBLK_OFF;
+    if (const char* v = std::getenv("SG_UBLK")) { if (v[0] == '0') e->dbg_flags |= UBLK_OFF; }
     if (const char* v = std::getenv("SG_RADIX_BELOW")) e->radix_below = std::strtoull(v, nullptr, 0);
     if (const char* v = std::getenv("SG_TOK_WIDE")) e->tok_wide = std::atoi(v) == 512 ? 512u : 1024u;
     if (const char* v = std::getenv("SG_TOK_LIGHT")) e->tok_light = (uint32_t)std::strtoul(v, nullptr, 0);
@@ -1566,6 +1578,15 @@ extern "C" unsigned int sgx_hot_marked(sg_engine* e) {
     if (!e) return 0;
     drain_hold(e);
     return e->hot_marked_last;
+}
+// diagnostics export: the pre-blocked placement of the last collected batch: [0] segments of PM_UBLK resources in
+// cooperative bins (SEG_UBLK), [1] in lane bins, [2] RF_UBLK words k_ublk_words wrote.  Returns the values written.
+extern "C" int sgx_preblocked_last(sg_engine* e, unsigned long long* out, int cap) {
+    if (!e || !out) return 0;
+    drain_hold(e);
+    int k = 0;
+    for (; k < 3 && k < cap; ++k) out[k] = e->ublk_last[k];
+    return k;
 }
 // diagnostics export: zero the SG_DEBUG counters ([20] is a running minimum)
 extern "C" int sgx_debug_reset(sg_engine* e) {
@@ -2727,6 +2748,7 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
     int64_t* d_t0 = reinterpret_cast<int64_t*>(e->d_bsmall + 4);  // [4..5]
     uint32_t *kin = e->d_k1, *vin = e->d_v1, *kout = e->d_k0, *vout = e->d_v0;
     if (++e->epoch == 0) e->epoch = 1;
+    const uint32_t ublk = (e->dbg_flags & UBLK_OFF) ? 0u : 1u;
     // every event through the radix passes: SG_DEBUG_FLAGS & 8192 (A/B of the group stage), or a batch of 2^30 events
     // or more (the hot / cold stage's words hold a position in 30 bits)
     B.radix = e->radix_group || n >= (1ull << 30) || n < e->radix_below;
@@ -2783,7 +2805,7 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
                               B.d_ashort, B.d_along, B.d_amulti, e->d_bsmall + 6, e->has_mix ? B.d_mix : nullptr,
                               (uint32_t)B.mix_cap, e->d_bsmall + 72, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
                               (e->dbg_flags & HEAD_OFF) ? 0u : e->head_min, e->d_hot_tab, e->nhot, e->d_bsmall + 80, need_hot,
-                              need_blk, bmax, skip_min, e->d_bsmall + 73, gs));
+                              need_blk, bmax, skip_min, e->d_bsmall + 73, e->d_bsmall + 74, gs));
         HIPCHK(launch_scan(e->d_blkcnt, e->d_blkcnt, (uint64_t)nblk * N_BINS, e->d_part, nullptr, gs));
         HIPCHK(launch_seg_order(e->d_segs, e->d_bsmall + 1, mb, e->d_blkcnt, e->d_order, e->d_bsmall + 8, gs));
         return SG_OK;
@@ -2801,7 +2823,7 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
     if (B.radix) {
         HIPCHK(launch_rs_first(dev_ev, n, R, e->gbase, e->d_ring, ring_mask, e->cfg.statistic_max_rt, e->d_rec_o,
                                e->d_k1, e->d_v1, e->d_hist, nblocks, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
-                               e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e), gs));
+                               e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e), ublk, gs));
         if (int drc = decide_prev()) return drc;
         for (int p = 0; p < passes; ++p) {
             if (p > 0) HIPCHK(launch_radix_hist(kin, n, p * db, e->d_hist, nblocks, gs));
@@ -2828,7 +2850,7 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
         HIPCHK(launch_grp_first(dev_ev, n, R, e->gbase, ring_mask, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
                                 e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e),
                                 e->d_hot_tab, nhot, nblocks,
-                                words, hot_off, e->d_k1, e->d_v1, ccnt, e->d_hist, gs));
+                                words, hot_off, e->d_k1, e->d_v1, ccnt, e->d_hist, ublk, gs));
         if (int drc = decide_prev()) return drc;
         HIPCHK(launch_hot_scan(hot_off, nblocks, nhot, e->d_hot_part, e->d_hot_hb, e->d_bsmall + 77, gs));
         HIPCHK(launch_cold_n(n, e->d_bsmall + 77, e->d_bsmall + 78, gs));
@@ -2865,7 +2887,7 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
         HIPCHK(launch_grp_records(dev_ev, n, e->gbase, ring_mask, e->cfg.statistic_max_rt, words, hot_off, nhot, nblocks,
                                   e->d_hot_hb, e->d_recs, vin, e->d_prev, e->d_bsmall + 3, e->d_bst,
                                   e->d_bsmall + 0, dev_ext, dev_args, SG_MAX_CONTEXTS, e->d_link, e->epoch, need_hot,
-                                  need_blk, gs));
+                                  need_blk, R, dev_auth(e), dev_auth_ids(e), ublk, gs));
         HIPCHK(launch_block_sums(e->d_recs, n, e->d_bst, e->d_link, e->epoch, e->d_bsmall + 0, kin, e->d_bsmall + 77,
                                  need_blk, gs));
     }
@@ -2876,7 +2898,8 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
         HIPCHK(launch_hot_build(e->d_segs, e->d_bsmall + 1, mb, hot_min, R, e->d_hot_tab, e->d_hot_list, e->nhot,
                                 e->d_bsmall + 76, gs));
     // [0] bflags [1] nseg [3] nprev [4..5] t0 [6..7] XF_MIX lists [8..8+N_BINS] bin offsets [72] wide XF_MIX events
-    // [73] hot ids marked for the side tables [76] the next batch's hot ids
+    // [73] hot ids marked for the side tables [74] PM_UBLK segments in cooperative bins (SEG_UBLK) [75] in lane bins
+    // [76] the next batch's hot ids
     static_assert(8 + N_BINS + 1 <= 72 && HEAD_WORDS == 77, "head layout");
     HIPCHK(hipMemcpyAsync(B.h_head, e->d_bsmall, HEAD_WORDS * 4, hipMemcpyDeviceToHost, gs));
     HIPCHK(hipEventRecord(B.ev[1], gs));
@@ -2905,6 +2928,8 @@ static int accept_grouped(sg_engine* e, bool drop = false) {
     if (!B.radix) e->nhot = std::min<uint32_t>(head[76], hot_max());
     if (drop) return SG_OK;
     B.hot_marked = head[73];
+    B.ublk_coop = head[74];
+    B.ublk_lane = head[75];
     const uint32_t bflags = head[0];
     if (bflags & BF_BAD_RES) return fail(SG_EINVAL, "event res_id >= max_resources");
     if (bflags & BF_BAD_REF)
@@ -2918,7 +2943,7 @@ static int accept_grouped(sg_engine* e, bool drop = false) {
     if (e->has_mix && head[7] && (e->pv_on || e->pvt_on) && head[72]) {
         if (int prc = ensure_pv(e, head[72], head[7])) return prc;
     }
-    e->inflight.push_back({B.g.set, B.hot_marked});
+    e->inflight.push_back({B.g.set, B.hot_marked, B.ublk_coop, B.ublk_lane});
     ++e->seq;
     e->last = k;
     e->cur = k ^ 1;
@@ -3117,6 +3142,11 @@ static int decide_enqueue(sg_engine* e, int k) {
     if (n_mix || n_mixw)
         HIPCHK(launch_pq_mix(0, e->d_recs, dev_ev, vin, e->d_segs, B.d_mix, n_mix, B.mix_cap, n_mixw, S, dc, t0,
                              e->d_dec, e->d_bsmall + 0, ps, pv_ran ? e->d_pvrest + 1 : nullptr, e->d_pvrest));
+    // Pre-blocked ENTRYs of the cooperative bins' segments (SEG_UBLK): their words and RF_PBLK after the param pre
+    // pass (whose block comes first) and before every owner; launched only in a batch that has such a segment
+    if (head[74])
+        HIPCHK(launch_ublk_words(e->d_recs, e->d_segs, e->d_order + off[BIN_J16], off[BIN_J8 + 1] - off[BIN_J16], e->d_dec,
+                                 e->d_bsmall + 119, ps));
     HIPCHK(hipEventRecord(e->fork, ps));
     auto lane_bins = [&]() -> int {
         {

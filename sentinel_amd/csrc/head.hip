@@ -825,6 +825,7 @@ __global__ __launch_bounds__(64 * (HD_ND + 3)) void k_head(const SEv* __restrict
     if (blockIdx.x >= m) return;
     const Seg sg = segs[order[blockIdx.x]];
     const Prog pg = S.prog[sg.res];
+    if (sg.bin & SEG_UBLK) return;  // pre-blocked ENTRYs (RF_UBLK): the cooperative owner's, which knows the class
     if (pg.xf & XF_HEADT) head_seg<false>(sh, recs, sg, pg, S, cfg, t0, dec, bflags);
     else if (pg.xf & XF_HEADR) head_seg<true>(sh, recs, sg, pg, S, cfg, t0, dec, bflags);
     // (else: the cooperative owner's segment)

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_first(const sg_event* __restr
                                                       const sg_event_ext* __restrict__ ext,
                                                       const sg_arg* __restrict__ args, uint64_t n_args,
                                                       uint32_t max_ctx, const AuthDesc* __restrict__ auth,
-                                                      const uint32_t* __restrict__ auth_ids) {
+                                                      const uint32_t* __restrict__ auth_ids, uint32_t ublk) {
     constexpr int NB = 1 << DB;
     __shared__ uint32_t h[NB];
     for (int i = threadIdx.x; i < NB; i += RS_THREADS) h[i] = 0;
@@ -89,13 +89,14 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_first(const sg_event* __restr
         r.cnt = e.count;
         r.rt = 0;
         r.kind = e.kind;
-        r.flags = (uint8_t)(e.flags & 0x3Fu);  // the ABI's SG_F_* bits only (RF_* are internal)
+        r.flags = (uint8_t)(e.flags & 0x1Fu);  // the ABI's SG_F_* bits only (RF_* are internal)
         r.code = RC_NONE;
         r.pad = 0;
         uint32_t mark = 0;  // PM_* marks for the resource
         uint64_t key0 = (e.flags & SG_F_HAS_ARG) ? e.aux : NO_KEY;
         uint32_t tag = 0;        // origin / context node tag (dev_types.h TAG_*)
         bool own_args = false;   // the event's args come from the table
+        bool preb = false;       // a pre-blocked ENTRY: SystemSlot's (the caller's flag) or the authority rule's
         if (ext) {  // sg_submit_ex: validate the event's args; a NullContext event is k_lane's
             const sg_event_ext x = ext[i];
             if (x.n_args > SG_MAX_ARGS || (uint64_t)x.arg_off + x.n_args > n_args) fl |= BF_BAD_ARGS;
@@ -122,11 +123,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_first(const sg_event* __restr
                 if (x.origin_id >> TAG_ORIGIN_BITS) mark |= PM_LANE;  // not packable: k_lane reads the ext itself
                 else tag = x.origin_id | (x.context_id << TAG_ORIGIN_BITS);
             }
-            // an ENTRY its resource's authority rule blocks is k_lane's, as an upstream block is (auth: null
+            // an ENTRY its resource's authority rule blocks is pre-blocked, as an upstream block is (auth: null
             // unless authority rules are loaded)
             if (auth && e.kind == SG_EV_ENTRY && x.origin_id != 0 && e.res_id < max_res &&
                 auth_blocks(auth, auth_ids, e.res_id, x.origin_id))
-                mark |= PM_LANE;
+                preb = true;
         }
         if (own_args) {  // the record's HAS_ARG: args[0] is a scalar (a k_pq check / thread-count key)
             r.flags = (uint8_t)((r.flags & ~SG_F_HAS_ARG) | (key0 != NO_KEY ? SG_F_HAS_ARG : 0));
@@ -139,10 +140,16 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_first(const sg_event* __restr
         if (e.kind == SG_EV_ENTRY) {
             // the arg an exit(count, args) of this ENTRY will decrement (ParamFlowStatisticExitCallback)
             if (key_ring) key_ring[(gbase + i) & ring_mask] = key0;
-            // a prioritized ENTRY makes the resource's borrow ring live; an upstream block is k_lane's (a
-            // separate mark array: this stage may run while the previous batch's decide stores NodeInfo)
+            // a prioritized ENTRY makes the resource's borrow ring live (a separate mark array: this stage may
+            // run while the previous batch's decide stores NodeInfo)
             if (e.flags & SG_F_PRIORITIZED) mark |= PM_PRIO;
-            if (e.flags & SG_F_BLOCKED_UPSTREAM) mark |= PM_LANE;
+            // a pre-blocked ENTRY: PM_UBLK and RF_UBLK on its record (the cooperative owners take it as a block whose
+            // word is written, dev_types.h); SG_UBLK=0: k_lane's, as everything PM_LANE marks
+            if (e.flags & SG_F_BLOCKED_UPSTREAM) preb = true;
+            if (preb) {
+                mark |= ublk ? PM_UBLK : PM_LANE;
+                if (ublk) r.flags |= RF_UBLK;
+            }
         } else {
             if (e.kind == SG_EV_EXIT) {
                 const int64_t raw = (int64_t)(e.aux >> 48);
@@ -220,7 +227,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_grp_first(const sg_event* __rest
                                                        uint32_t nblocks, uint32_t* __restrict__ words,
                                                        uint32_t* __restrict__ hot_hist, uint32_t* __restrict__ ckeys,
                                                        uint32_t* __restrict__ cvals, uint32_t* __restrict__ ccnt,
-                                                       uint32_t* __restrict__ chist) {
+                                                       uint32_t* __restrict__ chist, uint32_t ublk) {
     constexpr int NB = 1 << DB;
     __shared__ uint32_t wcnt[4][HOT_MAX];  // per-wave hot-id counts, then per-wave rank offsets
     __shared__ uint32_t h[NB];
@@ -277,13 +284,13 @@ __global__ __launch_bounds__(RS_THREADS) void k_grp_first(const sg_event* __rest
                 }
                 if (auth && e.kind == SG_EV_ENTRY && x.origin_id != 0 && e.res_id < max_res &&
                     auth_blocks(auth, auth_ids, e.res_id, x.origin_id))
-                    mark |= PM_LANE;  // (as k_rs_first)
+                    mark |= ublk ? PM_UBLK : PM_LANE;  // (as k_rs_first; k_grp_records tests again for RF_UBLK)
             }
             if (own_args && e.kind == SG_EV_EXIT && (e.flags & SG_F_EXIT_ARGS)) mark |= PM_XARGS;
             if (e.kind == SG_EV_ENTRY) {
                 if (key_ring) key_ring[(gbase + i) & ring_mask] = key0;
                 if (e.flags & SG_F_PRIORITIZED) mark |= PM_PRIO;
-                if (e.flags & SG_F_BLOCKED_UPSTREAM) mark |= PM_LANE;
+                if (e.flags & SG_F_BLOCKED_UPSTREAM) mark |= ublk ? PM_UBLK : PM_LANE;
             } else if (e.kind == SG_EV_EXIT && own_args && key_ring) {
                 key_ring[(gbase + i) & ring_mask] = key0;
             }
@@ -521,7 +528,9 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
                                                             const sg_arg* __restrict__ args, uint32_t max_ctx,
                                                             Link* __restrict__ link, uint32_t epoch,
                                                             const uint32_t* __restrict__ need_hot,
-                                                            const uint32_t* __restrict__ need_blk) {
+                                                            const uint32_t* __restrict__ need_blk, uint32_t max_res,
+                                                            const AuthDesc* __restrict__ auth,
+                                                            const uint32_t* __restrict__ auth_ids, uint32_t ublk) {
     __shared__ uint4 srec[GR_EVENTS];        // the quarter's hot records in (hot id, rank) order
     __shared__ uint32_t spos[GR_EVENTS], sval[GR_EVENTS];
     __shared__ uint32_t lo[HOT_MAX];         // per hot id: the quarter's count, then its first local slot
@@ -644,14 +653,19 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
             r.cnt = ee.count;
             r.rt = 0;
             r.kind = ee.kind;
-            r.flags = (uint8_t)(ee.flags & 0x3Fu);  // the ABI's SG_F_* bits only (RF_* are internal)
+            r.flags = (uint8_t)(ee.flags & 0x1Fu);  // the ABI's SG_F_* bits only (RF_* are internal)
             r.code = RC_NONE;
             r.pad = 0;
             uint32_t tag = 0;
             bool own_args = false;
             uint64_t key0 = (ee.flags & SG_F_HAS_ARG) ? ee.aux : NO_KEY;
+            // a pre-blocked ENTRY (k_grp_first marked its resource PM_UBLK by the same test)
+            bool preb = entry && (ee.flags & SG_F_BLOCKED_UPSTREAM);
             if (ext) {
                 const sg_event_ext x = ext[i];
+                if (auth && entry && x.origin_id != 0 && ee.res_id < max_res &&
+                    auth_blocks(auth, auth_ids, ee.res_id, x.origin_id))
+                    preb = true;
                 if (x.n_args && x.n_args <= SG_MAX_ARGS) {
                     const sg_arg a0 = args[x.arg_off];
                     key0 = a0.kind == SG_ARG_SCALAR ? a0.key : NO_KEY;
@@ -665,6 +679,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_grp_records(const sg_event* __re
                 if (ee.kind == SG_EV_EXIT) r.flags |= RF_OWN_ARGS;
             }
             r.x = tag;
+            if (preb && ublk) r.flags |= RF_UBLK;
             if (entry) {
                 zero |= ee.count == 0;
             } else {
@@ -1186,10 +1201,10 @@ hipError_t launch_rs_first(const sg_event* ev, uint64_t n, uint32_t max_res, uin
                            uint32_t* ghist, uint32_t nblocks, uint32_t* bflags, int64_t* t0_out, uint32_t* prio,
                            uint64_t* key_ring, const uint32_t* comp, const sg_event_ext* ext, const sg_arg* args,
                            uint64_t n_args, uint32_t max_ctx, const AuthDesc* auth, const uint32_t* auth_ids,
-                           hipStream_t st) {
+                           uint32_t ublk, hipStream_t st) {
     hipLaunchKernelGGL(k_rs_first<8>, dim3(nblocks), dim3(RS_THREADS), 0, st, ev, n, max_res, gbase, ring, ring_mask,
                        max_rt, rec_o, keys, vals, ghist, nblocks, bflags, t0_out, prio, key_ring, comp, ext, args,
-                       n_args, max_ctx, auth, auth_ids);
+                       n_args, max_ctx, auth, auth_ids, ublk);
     return hipGetLastError();
 }
 hipError_t launch_radix_hist(const uint32_t* keys, uint64_t n, int shift, uint32_t* ghist, uint32_t nblocks,
@@ -1232,10 +1247,10 @@ hipError_t launch_grp_first(const sg_event* ev, uint64_t n, uint32_t max_res, ui
                             const AuthDesc* auth, const uint32_t* auth_ids,
                             const uint16_t* hot_tab, uint32_t nhot, uint32_t nblocks, uint32_t* words,
                             uint32_t* hot_hist, uint32_t* ckeys, uint32_t* cvals, uint32_t* ccnt, uint32_t* chist,
-                            hipStream_t st) {
+                            uint32_t ublk, hipStream_t st) {
     hipLaunchKernelGGL(k_grp_first<8>, dim3(nblocks), dim3(RS_THREADS), 0, st, ev, n, max_res, gbase, ring_mask, bflags,
                        t0_out, prio, key_ring, comp, ext, args, n_args, max_ctx, auth, auth_ids, hot_tab, nhot, nblocks, words,
-                       hot_hist, ckeys, cvals, ccnt, chist);
+                       hot_hist, ckeys, cvals, ccnt, chist, ublk);
     return hipGetLastError();
 }
 hipError_t launch_hot_scan(uint32_t* C, uint32_t nblocks, uint32_t nhot, uint32_t* part, uint32_t* hb, uint32_t* total,
@@ -1261,10 +1276,11 @@ hipError_t launch_grp_records(const sg_event* ev, uint64_t n, uint64_t gbase, ui
                               const uint32_t* hb, SEv* recs, uint32_t* svals, uint32_t* prev,
                               uint32_t* nprev, uint32_t* bst, uint32_t* bflags, const sg_event_ext* ext,
                               const sg_arg* args, uint32_t max_ctx, Link* link, uint32_t epoch,
-                              const uint32_t* need_hot, const uint32_t* need_blk, hipStream_t st) {
+                              const uint32_t* need_hot, const uint32_t* need_blk, uint32_t max_res,
+                              const AuthDesc* auth, const uint32_t* auth_ids, uint32_t ublk, hipStream_t st) {
     hipLaunchKernelGGL(k_grp_records, dim3(nblocks * 4), dim3(GR_THREADS), 0, st, ev, n, gbase, ring_mask, max_rt, words, P,
                        nhot, nblocks, hb, recs, svals, prev, nprev, bst, bflags, ext, args, max_ctx, link, epoch, need_hot,
-                       need_blk);
+                       need_blk, max_res, auth, auth_ids, ublk);
     return hipGetLastError();
 }
 hipError_t launch_hot_segs(const uint32_t* hb, uint32_t nhot, const uint32_t* hot_list, Seg* segs, uint32_t* out,

@@ -302,6 +302,19 @@ class Engine:
         fn.argtypes = [C.c_void_p]
         return int(fn(self.h))
 
+    def preblocked_stats(self):
+        """Where the last collected batch placed the resources that have seen a pre-blocked ENTRY
+        (SG_F_BLOCKED_UPSTREAM, or one its authority rule blocks): [0] their segments in cooperative bins, [1] in
+        lane bins, [2] pre-blocked decision words written ahead of the cooperative owners (diagnostics export
+        sgx_preblocked_last; drains the pipeline first)."""
+        fn = lib().sgx_preblocked_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        out = np.zeros(3, dtype=np.uint64)
+        if fn(self.h, out.ctypes.data, 3) != 3:
+            raise SentinelError(A.SG_EDEVICE, "sgx_preblocked_last failed")
+        return [int(v) for v in out]
+
     def read_aux_node(self, res: int, kind: int, node_id: int):
         """An origin (kind 0, origin id) / context (kind 1, context id) node of res: second window [2, 8], thread,
         minute pass history [2, 2] ({ws, pass} per second parity); None if absent (diagnostics export
