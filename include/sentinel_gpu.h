@@ -185,7 +185,10 @@ enum {
     SG_F_HAS_ARG = 1u << 1,     /* args = {args[0]}, non-null; aux = its interned 64-bit key (ENTRY; sg_submit_ex
                                    with ext.n_args > 0 takes the args from the table instead) */
     SG_F_EXIT_ARGS = 1u << 2,   /* Entry.exit(count, args): param thread counts are released (EXIT), SURVEY Q14 */
-    SG_F_ENTRY_OUT = 1u << 3,   /* EntryType.OUT (ENTRY); informational (SystemSlot is out of scope) */
+    SG_F_ENTRY_OUT = 1u << 3,   /* EntryType.OUT (ENTRY, and the EXIT of such an ENTRY: an EXIT carries the flag iff its
+                                   ENTRY did, the Entry keeps its ResourceWrapper).  No check reads it (SystemSlot is
+                                   out of scope); events with the flag are not counted on the global inbound node
+                                   (sg_track_inbound) */
     SG_F_BLOCKED_UPSTREAM = 1u << 4 /* ENTRY: the caller's SystemSlot threw (or an AuthoritySlot the caller chose to keep
                                    instead of sg_load_authority_rules).  Those slots sit between ParamFlowSlot and
                                    FlowSlot (param/slots/HotParamSlotChainBuilder.java:39-50), so the param checks still
@@ -461,8 +464,36 @@ int sg_intern_context(sg_engine* e, const char* context, uint32_t* out_id);
 
 /* Per-second MetricNode export: StatisticNode.metrics() of every ClusterNode
  * (core/node/StatisticNode.java:124-151, core/node/metric/MetricTimerListener.java:39-71).
- * Writes up to cap nodes, *n receives the number written. */
+ * Writes up to cap nodes, *n receives the number of rows there are (a cap below it truncates the output only). */
 int sg_snapshot_metrics(sg_engine* e, int64_t now_ms, sg_metric_node* out, uint64_t cap, uint64_t* n);
+
+/* The global inbound node, Constants.ENTRY_NODE: StatisticSlot counts every EntryType.IN entry and its exit on it as
+ * well as on the resource's ClusterNode (core/slots/statistic/StatisticSlot.java:72-76, 89-92, 107-110, 158-161).
+ * MetricTimerListener writes its metrics() as the row Constants.TOTAL_IN_RESOURCE_NAME of the metric log
+ * (core/node/metric/MetricTimerListener.java:48); SystemRuleManager.checkSystem and SystemStatusListener read its
+ * second window and thread count.  No decision of the engine reads it.
+ *
+ * sg_track_inbound: tracking is off by default, and an engine on which this is never called does what it did without
+ * it.  on = 1 is accepted only before the engine has accepted its first batch (SG_ESTATE afterwards: the entries of
+ * later exits would never have been counted); on = 0 at any time: counting stops, the node stays readable.  The same
+ * value twice is a no-op.  While tracking is on, the events without SG_F_ENTRY_OUT update the node from their final
+ * verdicts: an ENTRY of status SG_PASS adds pass += count and one thread, SG_PASS_WAIT the thread alone
+ * (StatisticSlot.java:82-92), a blocked one (status 2, 3, 4, 6, 7) block += count, SG_NO_CHECK nothing; an effective
+ * EXIT (the ClusterNode's rule) adds success += count, rt += the clipped rt once, minRt, and takes one thread; a TRACE
+ * nothing.  Exception and occupied pass stay 0 and the borrow ring stays empty.  A refused batch leaves the node as
+ * it was.
+ * sg_read_inbound_node waits for every batch like sg_read_node and fills the same struct (has_chain = 1);
+ * SG_ESTATE if tracking was never turned on.
+ * sg_inbound_metrics is a read-back (no bucket of the node is created or reset): [0] passQps [1] blockQps
+ * [2] successQps [3] exceptionQps [4] totalQps [5] avgRt [6] minRt [7] maxSuccessQps [8] curThreadNum at now_ms
+ * (core/node/StatisticNode.java:153-260).  Writes up to cap values and returns how many (0 on an error).
+ * With tracking on, sg_snapshot_metrics appends the node's metrics() rows after the ClusterNodes' rows, with
+ * res_id = SG_RES_TOTAL_INBOUND; the node has a lastFetchTime of its own. */
+#define SG_RES_TOTAL_INBOUND 0xFFFFFFFFu                      /* res_id of the node's sg_metric_node rows */
+#define SG_TOTAL_IN_RESOURCE_NAME "__total_inbound_traffic__" /* Constants.TOTAL_IN_RESOURCE_NAME */
+int sg_track_inbound(sg_engine* e, int32_t on);
+int sg_read_inbound_node(sg_engine* e, int64_t now_ms, sg_node_state* out);
+int sg_inbound_metrics(sg_engine* e, int64_t now_ms, double* out, int cap);
 
 /* Batched TokenService.requestToken (core/cluster/TokenService.java:26-35,
  * csrv/flow/DefaultTokenService.java:37-48).  Rules come from the flow rules

@@ -187,7 +187,9 @@ public class GpuDecisionSlot extends AbstractLinkedProcessorSlot<DefaultNode> {
             long rtRaw = now - cur.getCreateTime();
             boolean withArgs = args != null && args.length > 0 && ParamFlowRuleManager.hasRules(resourceWrapper.getName());
             eng.post(new GpuEngine.Op(now, entry.resId, count, SentinelGpu.EV_EXIT,
-                                      withArgs ? SentinelGpu.F_EXIT_ARGS : 0,
+                                      (withArgs ? SentinelGpu.F_EXIT_ARGS : 0)
+                                      // an EXIT carries F_ENTRY_OUT iff its ENTRY did (the engine's inbound node)
+                                      | (resourceWrapper.getType() == EntryType.OUT ? SentinelGpu.F_ENTRY_OUT : 0),
                                       SentinelGpu.auxExit(GpuEngine.indexOf(entry), rtRaw), entry.origin,
                                       entry.context, withArgs ? args : null, null));
             if (resourceWrapper.getType() == EntryType.IN) {

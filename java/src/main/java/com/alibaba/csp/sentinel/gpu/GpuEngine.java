@@ -127,6 +127,9 @@ final class GpuEngine {
             MemorySegment out = arena.allocate(ADDRESS);
             SentinelGpu.check((int)SentinelGpu.ENGINE_CREATE.invokeExact(cfg, out));
             handle = out.get(ADDRESS, 0);
+            // Constants.ENTRY_NODE on the device as well (accepted before the first batch only): its rows of the
+            // snapshot are the __total_inbound_traffic__ lines; the SystemSlot check keeps reading the JVM's node
+            SentinelGpu.check((int)SentinelGpu.TRACK_INBOUND.invokeExact(handle, 1));
         } catch (RuntimeException ex) {
             throw ex;
         } catch (Throwable t) {

@@ -246,6 +246,15 @@ final class SentinelGpu {
     static final MethodHandle CLUSTER_NAMESPACE_QPS = fn("sg_cluster_namespace_qps",
         rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS));
     static final MethodHandle READ_NODE =fn("sg_read_node", rc(ADDRESS, JAVA_INT, JAVA_LONG, ADDRESS));
+    /** The global inbound node (Constants.ENTRY_NODE on the device): (engine, on) / (engine, now, sg_node_state* out) /
+     *  (engine, now, double* out, cap) -> values written (passQps, blockQps, successQps, exceptionQps, totalQps,
+     *  avgRt, minRt, maxSuccessQps, curThreadNum). */
+    static final MethodHandle TRACK_INBOUND = fn("sg_track_inbound", rc(ADDRESS, JAVA_INT));
+    static final MethodHandle READ_INBOUND_NODE = fn("sg_read_inbound_node", rc(ADDRESS, JAVA_LONG, ADDRESS));
+    static final MethodHandle INBOUND_METRICS = fn("sg_inbound_metrics", rc(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT));
+    /** res_id of the inbound node's sg_metric_node rows, and the name they are logged under. */
+    static final int RES_TOTAL_INBOUND = 0xFFFFFFFF;
+    static final String TOTAL_IN_RESOURCE_NAME = "__total_inbound_traffic__";
     /** ParameterMetric.getThreadCount(paramIdx, value): (engine, res, paramIdx, key, long* count, int* present). */
     static final MethodHandle PARAM_THREAD_COUNT =
         fn("sg_param_thread_count", rc(ADDRESS, JAVA_INT, JAVA_INT, JAVA_LONG, ADDRESS, ADDRESS));

@@ -45,6 +45,9 @@ F_ENTRY_OUT = 1 << 3
 F_BLOCKED_UPSTREAM = 1 << 4
 REF_NONE = 0xFFFFFFFFFFFF
 ARG_NULL, ARG_SCALAR, ARG_LIST = 0, 1, 2
+RES_TOTAL_INBOUND = 0xFFFFFFFF  # res_id of the global inbound node's metric rows (sg_track_inbound)
+TOTAL_IN_RESOURCE_NAME = "__total_inbound_traffic__"  # Constants.TOTAL_IN_RESOURCE_NAME
+
 MAX_ARGS = 24
 MAX_CONTEXTS = 2000
 

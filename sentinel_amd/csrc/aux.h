@@ -15,6 +15,35 @@
 
 namespace sg {
 
+// What StatisticSlot does for an event on the nodes beside the ClusterNode (origin, context, ENTRY_NODE), read off
+// the committed verdicts (StatisticSlot.java:54-173): a passed ENTRY adds pass and one thread, a PriorityWait one the
+// thread alone (its pass was borrowed on the ClusterNode), a blocked one adds block, an effective EXIT success, rt and
+// minRt and takes the thread back; a Tracer exception reaches the ClusterNode only.
+enum : uint32_t { AW_NONE = 0, AW_PASS = 1, AW_BLOCK = 2, AW_EXIT = 3, AW_WAIT = 4 };
+
+// chain: whether the event's resource has its slot chain, read for an RC_NONE EXIT only (no reference: effective iff
+// the chain exists); *tag: the node tag of the ENTRY the event belongs to (sg_submit_ex).  p: sorted position.
+__device__ __forceinline__ uint32_t stat_what(const SEv& r, uint32_t p, const SEv* __restrict__ recs,
+                                              const uint32_t* __restrict__ dec, bool chain, uint32_t* tag) {
+    if (r.kind == SG_EV_ENTRY) {
+        const uint32_t st = dec[p] & 0xFFu;
+        *tag = r.x;
+        if (st == ST_NO_CHECK || st == ST_NOT_ENTRY) return AW_NONE;
+        return st == ST_PASS ? AW_PASS : st == ST_PASS_WAIT ? AW_WAIT : AW_BLOCK;
+    }
+    if (r.kind != SG_EV_EXIT) return AW_NONE;  // Tracer: the ClusterNode only
+    bool eff;
+    uint32_t tg = r.x;
+    if (r.code == RC_NONE) eff = chain;
+    else if (r.code == RC_PASSED) eff = true;
+    else if (r.code == RC_BATCH) {
+        eff = st_passed(dec[r.x] & 0xFFu);
+        tg = recs[r.x].x;  // the ENTRY's nodes (its Context)
+    } else eff = false;
+    *tag = tg;
+    return eff ? AW_EXIT : AW_NONE;
+}
+
 __device__ __forceinline__ void aux_init(AuxNode* a) {
     a->thread = 0;
     a->flags = 0;

@@ -35,28 +35,13 @@ using namespace sg;
 #define AUX_NONE 0x7FFFFFFF
 #define AUX_EMPTY32 0xFFFFFFFFu
 
-enum : uint32_t { AW_NONE = 0, AW_PASS = 1, AW_BLOCK = 2, AW_EXIT = 3 };
-
-// What event p (segment-relative nothing: absolute sorted position) does to its nodes, from the verdicts.
+// What event p (segment-relative nothing: absolute sorted position) does to its nodes, from the verdicts: aux.h
+// stat_what, which the ENTRY_NODE pass (inbound.hip) shares.  (A PriorityWait ENTRY is k_lane's alone: the resource
+// of a prioritized entry keeps its lane, which updates the nodes itself.)
 __device__ __forceinline__ uint32_t aux_what(const SEv& r, uint32_t p, const SEv* __restrict__ recs,
                                              const uint32_t* __restrict__ dec, bool chain, uint32_t* tag) {
-    if (r.kind == SG_EV_ENTRY) {
-        const uint32_t st = dec[p] & 0xFFu;
-        *tag = r.x;
-        if (st == ST_NO_CHECK || st == ST_NOT_ENTRY) return AW_NONE;
-        return st == ST_PASS ? AW_PASS : st == ST_PASS_WAIT ? AW_NONE : AW_BLOCK;  // (PASS_WAIT: k_lane only)
-    }
-    if (r.kind != SG_EV_EXIT) return AW_NONE;  // Tracer: the ClusterNode only
-    bool eff;
-    uint32_t tg = r.x;
-    if (r.code == RC_NONE) eff = chain;
-    else if (r.code == RC_PASSED) eff = true;
-    else if (r.code == RC_BATCH) {
-        eff = st_passed(dec[r.x] & 0xFFu);
-        tg = recs[r.x].x;  // the ENTRY's nodes (its Context)
-    } else eff = false;
-    *tag = tg;
-    return eff ? AW_EXIT : AW_NONE;
+    const uint32_t w = stat_what(r, p, recs, dec, chain, tag);
+    return w == AW_WAIT ? AW_NONE : w;
 }
 
 // ---------------------------------------------------------------- sequential form (lanes, fallback)

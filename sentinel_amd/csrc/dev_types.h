@@ -434,6 +434,30 @@ struct AuxAcc {
 static_assert(sizeof(AuxAcc) == 128, "AuxAcc size");
 #define AUX_PIECE 4096u      // aux.hip: events of a long segment per piece workgroup
 
+// The global inbound node, Constants.ENTRY_NODE (inbound.hip): a ClusterNode without rules that StatisticSlot counts
+// every EntryType.IN entry and exit on (StatisticSlot.java:72-76, 89-92, 107-110, 158-161).  One node an engine, in an
+// allocation of its own (made by the first sg_track_inbound): both windows in full, as every reader of it wants them
+// (MetricTimerListener its minute window, SystemRuleManager / SystemStatusListener its second window and thread count).
+#define INB_SLOTS 62         // 2 second-window buckets, then the 60 minute-window buckets
+#define INB_TILE 4096u       // records a workgroup folds between two 64-bit folds (4,096 x 65,535 < 2^32)
+#define INB_MAX_WG 1024u     // partials a batch can leave (a few workgroups a CU)
+struct InbNode {
+    Bkt sec[2];              // rollingCounterInSecond (its borrow ring stays empty: nothing occupies on this node)
+    Bkt minb[60];            // rollingCounterInMinute
+    int32_t thread;          // curThreadNum
+    uint32_t last[3];        // of the last batch: workgroups that left a partial, records visited, updates counted
+    int64_t last_fetch;      // StatisticNode.lastFetchTime of its metrics()
+};
+// what one workgroup's tiles add up to: per slot the latest window its events fall in (an index relative to the batch,
+// 500 ms units for the second window, seconds for the minute window; -1: none) and the sums of the events in it
+struct InbPart {
+    int32_t W[64];
+    uint64_t s[64][4];       // pass, block, success, rt
+    uint32_t minrt[64];      // 0xFFFFFFFF: none
+    int32_t thread;
+    uint32_t visited, updates, pad;
+};
+
 struct DevState {
     Bkt* sec;
     int64_t* borrow;          // [res][2 slots] x {ws, pass}: FutureBucketLeapArray of the second window

@@ -107,6 +107,9 @@ hipError_t launch_aux(const SEv* recs, const Seg* segs, const uint32_t* aux, con
                       uint32_t* bflags, hipStream_t st);
 hipError_t launch_aux_cold(const SEv* recs, const Seg* segs, const uint32_t* aux, const uint32_t* ashort, const DevState& S,
                            const DevCfg& cfg, int64_t t0, const uint32_t* dec, uint32_t* bflags, hipStream_t st);
+// inbound.hip
+hipError_t launch_inbound(const SEv* recs, const uint32_t* dec, uint64_t n, const sg_event* ev, const uint32_t* vals,
+                          const DevState& S, const DevCfg& cfg, int64_t t0, InbPart* part, InbNode* node, hipStream_t st);
 // param.hip
 hipError_t launch_pq(int wide, const SEv* recs, const sg_event* ev, const uint32_t* vals, const Seg* segs,
                      const uint32_t* order, uint32_t m, const DevState& S, const DevCfg& cfg, int64_t t0, uint32_t* dec,
@@ -649,6 +652,11 @@ struct sg_engine {
     uint32_t* d_edges = nullptr;
     uint32_t hot_marked_last = 0;  // hot ids marked for the side tables in the last collected batch (sgx_hot_marked)
     uint32_t ublk_last[3] = {0, 0, 0};  // sgx_preblocked_last: PM_UBLK segments in cooperative / lane bins, RF_UBLK words
+    // the global inbound node, Constants.ENTRY_NODE (inbound.hip): allocated by the first sg_track_inbound(1); inb_on:
+    // batches are counted on it, inb_ever: it exists (readable after tracking was turned off)
+    InbNode* d_inb = nullptr;
+    InbPart* d_inbpart = nullptr;
+    bool inb_on = false, inb_ever = false;
     bool radix_group = false;    // SG_DEBUG_FLAGS & 8192: the all-radix group stage (A/B)
     uint64_t radix_below = 1u << 18;  // SG_RADIX_BELOW: batches of fewer events take the radix group stage (the drop-in's
                                       // 65,536-event batches: 36 vs 30-32 M entries/s on the hot / cold one)
@@ -1696,6 +1704,7 @@ int sg_engine_destroy(sg_engine* e) {
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_nslimit); dfree(e->d_nsb); dfree(e->d_borrow); dfree(e->d_keyring);
     dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx); dfree(e->d_tbounds);
     dfree(e->d_snap_cnt); dfree(e->d_snap_off); dfree(e->d_snap_out); dfree(e->d_dbg);
+    dfree(e->d_inb); dfree(e->d_inbpart);
     dfree(e->d_ks_key); dfree(e->d_ks_idx); dfree(e->d_ks_marks);
     for (auto& v : e->ks_ev) if (v) (void)hipEventDestroy(v);
     dfree(e->d_pvcnt); dfree(e->d_pvspare); dfree(e->d_ptst); dfree(e->d_ptserial); dfree(e->d_ptdedup);
@@ -3267,6 +3276,9 @@ static int decide_enqueue(sg_engine* e, int k) {
         HIPCHK(launch_aux(e->d_recs, e->d_segs, e->d_bsmall + 130, aux_early ? nullptr : B.d_ashort, B.d_along, B.d_apiece,
                           B.d_amulti, S, dc, t0, e->d_dec, e->d_auxpool, e->auxpool_cap, e->d_bsmall + 134, e->d_auxmeta,
                           e->d_bsmall + 0, st));
+    // the global inbound node from the same verdicts (inbound.hip), when it is tracked
+    if (e->inb_on)
+        HIPCHK(launch_inbound(e->d_recs, e->d_dec, n, dev_ev, vin, S, dc, t0, e->d_inbpart, e->d_inb, st));
     HIPCHK(hipEventRecord(B.ev[3], st));
     // ---- 4. decisions back to submission order + status ring
     if (B.radix) HIPCHK(launch_post(e->d_posof, e->d_dec, n, G.gbase, e->d_ring, ring_mask, dev_out, st));
@@ -3448,6 +3460,14 @@ static int tiny_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext, 
         return fail(SG_EINVAL, "an sg_event_ext names args outside the table (or more than SG_MAX_ARGS, or a bad kind)");
     }
     e->gbase += n;
+    // the global inbound node: the two kernels of the batched path behind a call k_tiny decided (recs, dec and the
+    // submission indices are in global memory); the caller's buffers are free again when this returns
+    if (e->inb_on) {
+        int64_t t0 = 0;
+        HIPCHK(hipMemcpy(&t0, &dev_ev[0].ts, 8, hipMemcpyDeviceToHost));
+        HIPCHK(launch_inbound(e->d_recs, e->d_dec, n, dev_ev, e->d_v0, S, dc, t0, e->d_inbpart, e->d_inb, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
     // the decide stage's own flags (collect)
     if (bflags & BF_BAD_REF)
         return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
@@ -3630,12 +3650,52 @@ int sg_read_node(sg_engine* e, uint32_t res, int64_t now_ms, sg_node_state* out)
     return SG_OK;
 }
 
+// StatisticNode.metrics() of the global inbound node, appended to the *n ClusterNode rows of a snapshot (the pipeline
+// is drained): details() creates / resets the bucket of now as k_snap_count does for a ClusterNode, then the buckets
+// after the node's own lastFetchTime and before the current second are the rows, in slot order.  One node's 60 buckets:
+// host arithmetic on a copy, written back.
+static int snapshot_inbound(sg_engine* e, int64_t now_ms, sg_metric_node* out, uint64_t cap, uint64_t* n) {
+    InbNode nd;
+    HIPCHK(hipMemcpy(&nd, e->d_inb, sizeof(nd), hipMemcpyDeviceToHost));
+    const int64_t cur = now_ms - now_ms % 1000;
+    if (now_ms >= 0) {
+        Bkt& c = nd.minb[(now_ms / 1000) % 60];
+        if (c.ws < cur) { std::memset(&c, 0, sizeof(c)); c.ws = cur; c.minrt = e->cfg.statistic_max_rt; }
+    }
+    std::vector<sg_metric_node> rows;
+    int64_t nl = nd.last_fetch;
+    for (const Bkt& b : nd.minb) {
+        if (b.ws < 0 || now_ms - b.ws > 60000) continue;
+        const int64_t rt = b.succ != 0 ? b.rt / b.succ : b.rt;
+        if (!(b.ws > nd.last_fetch && b.ws < cur)) continue;
+        if (!(b.pass > 0 || b.block > 0 || b.succ > 0 || b.exc > 0 || rt > 0 || b.occ > 0)) continue;
+        sg_metric_node m;
+        std::memset(&m, 0, sizeof(m));
+        m.timestamp = b.ws; m.pass_qps = b.pass; m.block_qps = b.block; m.success_qps = b.succ;
+        m.exception_qps = b.exc; m.rt = rt; m.occupied_pass_qps = b.occ; m.res_id = SG_RES_TOTAL_INBOUND;
+        rows.push_back(m);
+        nl = std::max(nl, b.ws);
+    }
+    nd.last_fetch = nl;
+    HIPCHK(hipMemcpy(e->d_inb, &nd, sizeof(nd), hipMemcpyHostToDevice));
+    const uint64_t base = *n;
+    if (out && base < cap && !rows.empty()) {
+        const uint64_t k = std::min<uint64_t>(rows.size(), cap - base);
+        HIPCHK(hipMemcpy(out + base, rows.data(), k * sizeof(sg_metric_node), hipMemcpyDefault));
+    }
+    *n = base + rows.size();
+    return SG_OK;
+}
+
 int sg_snapshot_metrics(sg_engine* e, int64_t now_ms, sg_metric_node* out, uint64_t cap, uint64_t* n) {
     if (!e || !n) return fail(SG_EINVAL, "null argument");
     HIPCHK(hipSetDevice(e->device));
     if (int rc = drain(e)) return rc;
     uint32_t R = (uint32_t)std::min<size_t>(e->names.size(), e->cfg.max_resources);
-    if (R == 0) { *n = 0; return SG_OK; }
+    if (R == 0) {
+        *n = 0;
+        return e->inb_on ? snapshot_inbound(e, now_ms, out, cap, n) : SG_OK;
+    }
     if (!e->d_snap_cnt) {
         HIPCHK(hipMalloc(&e->d_snap_cnt, (uint64_t)e->cfg.max_resources * 4));
         HIPCHK(hipMalloc(&e->d_snap_off, (uint64_t)e->cfg.max_resources * 4));
@@ -3660,7 +3720,98 @@ int sg_snapshot_metrics(sg_engine* e, int64_t now_ms, sg_metric_node* out, uint6
     if (k && out && !dev_out)
         HIPCHK(hipMemcpy(out, e->d_snap_out, k * sizeof(sg_metric_node), hipMemcpyDeviceToHost));
     *n = total;
+    return e->inb_on ? snapshot_inbound(e, now_ms, out, cap, n) : SG_OK;
+}
+
+int sg_track_inbound(sg_engine* e, int32_t on) {
+    if (!e) return fail(SG_EINVAL, "null engine");
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = drain(e)) return rc;
+    if ((on != 0) == e->inb_on) return SG_OK;
+    if (!on) { e->inb_on = false; return SG_OK; }  // the node stays readable
+    // entries of the batches before this call were never counted: their exits would take threads the node never had
+    if (e->gbase != 0) return fail(SG_ESTATE, "sg_track_inbound(1) after the first accepted batch");
+    if (!e->d_inb) {
+        HIPCHK(hipMalloc(&e->d_inb, sizeof(InbNode)));
+        HIPCHK(hipMalloc(&e->d_inbpart, (size_t)INB_MAX_WG * sizeof(InbPart)));
+        InbNode z;
+        std::memset(&z, 0, sizeof(z));
+        for (auto& b : z.sec) b.ws = -1;
+        for (auto& b : z.minb) b.ws = -1;
+        z.last_fetch = -1;
+        HIPCHK(hipMemcpy(e->d_inb, &z, sizeof(z), hipMemcpyHostToDevice));
+    }
+    e->inb_on = e->inb_ever = true;
     return SG_OK;
+}
+
+// the node on the host, every batch counted
+static int inbound_fetch(sg_engine* e, InbNode* nd) {
+    if (!e->inb_ever) return fail(SG_ESTATE, "the inbound node was never tracked (sg_track_inbound)");
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = drain(e)) return rc;
+    HIPCHK(hipMemcpy(nd, e->d_inb, sizeof(*nd), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+
+int sg_read_inbound_node(sg_engine* e, int64_t now_ms, sg_node_state* out) {
+    (void)now_ms;
+    if (!e || !out) return fail(SG_EINVAL, "null argument");
+    InbNode nd;
+    if (int rc = inbound_fetch(e, &nd)) return rc;
+    std::memset(out, 0, sizeof(*out));
+    auto ex = [](const Bkt& b, sg_bucket& o) {
+        if (b.ws < 0) { std::memset(&o, 0, sizeof(o)); o.window_start = -1; return; }
+        o.window_start = b.ws; o.pass = b.pass; o.block = b.block; o.exception = b.exc; o.success = b.succ;
+        o.rt = b.rt; o.occupied_pass = b.occ; o.min_rt = b.minrt;
+    };
+    for (int i = 0; i < 8; ++i) { out->second[i].window_start = -1; out->borrow[i].window_start = -1; }
+    ex(nd.sec[0], out->second[0]);
+    ex(nd.sec[1], out->second[1]);
+    for (int i = 0; i < 60; ++i) ex(nd.minb[i], out->minute[i]);
+    out->cur_thread_num = nd.thread;
+    out->has_chain = 1;
+    return SG_OK;
+}
+
+// What SystemRuleManager.checkSystem and SystemStatusListener read of ENTRY_NODE (StatisticNode.java:153-260), on a
+// copy of its second window: ArrayMetric reads take data.currentWindow() first, so the bucket of now counts as reset
+// when it holds an older window -- on the copy only, the node keeps its buckets.
+int sg_inbound_metrics(sg_engine* e, int64_t now_ms, double* out, int cap) {
+    if (!e || !out) return 0;
+    InbNode nd;
+    if (inbound_fetch(e, &nd)) return 0;
+    const int64_t max_rt = e->cfg.statistic_max_rt;
+    if (now_ms >= 0) {
+        Bkt& c = nd.sec[(now_ms / 500) & 1];
+        const int64_t ws = now_ms - now_ms % 500;
+        if (c.ws < ws) { std::memset(&c, 0, sizeof(c)); c.ws = ws; c.minrt = max_rt; }
+    }
+    int64_t pass = 0, block = 0, succ = 0, exc = 0, rt = 0, min_rt = max_rt, max_succ = 0;
+    for (const Bkt& b : nd.sec) {
+        if (b.ws < 0 || now_ms - b.ws > 1000) continue;  // LeapArray.isWindowDeprecated
+        pass += b.pass; block += b.block; succ += b.succ; exc += b.exc; rt += b.rt;
+        min_rt = std::min(min_rt, b.minrt);
+        max_succ = std::max(max_succ, b.succ);
+    }
+    const double v[9] = {(double)pass, (double)block, (double)succ, (double)exc, (double)pass + (double)block,
+                         succ ? (double)rt / (double)succ : 0.0, (double)std::max<int64_t>(min_rt, 1),
+                         (double)std::max<int64_t>(max_succ, 1) * 2.0, (double)nd.thread};
+    int k = 0;
+    for (; k < 9 && k < cap; ++k) out[k] = v[k];
+    return k;
+}
+
+// diagnostics export: the inbound pass of the last collected batch: [0] workgroups that left a partial, [1] records
+// visited, [2] updates counted.  Returns the values written.
+extern "C" int sgx_inbound_last(sg_engine* e, unsigned long long* out, int cap) {
+    if (!e || !out || !e->inb_ever) return 0;
+    drain_hold(e);
+    InbNode nd;
+    if (hipMemcpy(&nd, e->d_inb, sizeof(nd), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    int k = 0;
+    for (; k < 3 && k < cap; ++k) out[k] = nd.last[k];
+    return k;
 }
 
 int sg_cluster_set_connected_count(sg_engine* e, int64_t flow_id, int32_t connected) {

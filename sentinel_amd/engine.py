@@ -28,6 +28,7 @@ EXPORTS = (
     "sg_cluster_namespace", "sg_cluster_assign_flows", "sg_cluster_set_namespace_connected",
     "sg_cluster_namespace_qps", "sg_load_authority_rules", "sg_param_intern", "sg_param_intern_batch",
     "sg_param_keys_sweep", "sg_param_keys_stats", "sg_cluster_param_table_stats",
+    "sg_track_inbound", "sg_read_inbound_node", "sg_inbound_metrics",
 )
 
 
@@ -80,6 +81,22 @@ def lib():
         L.sg_last_timings.argtypes = [P, C.POINTER(C.c_double), C.c_int]
         _lib = L
     return _lib
+
+
+# the global inbound node's entry points, bound on first use: SG_LIB_PATH may name an older build of the library (the
+# A/B runs of bench.py against a parent commit), which loads as long as nothing asks it for them
+_INBOUND_ARGS = {
+    "sg_track_inbound": lambda: [C.c_void_p, C.c_int32],
+    "sg_read_inbound_node": lambda: [C.c_void_p, C.c_int64, C.POINTER(A.SgNodeState)],
+    "sg_inbound_metrics": lambda: [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int],
+}
+
+
+def _inbound(name):
+    fn = getattr(lib(), name)
+    if fn.argtypes is None:
+        fn.argtypes = _INBOUND_ARGS[name]()
+    return fn
 
 
 def _check(rc: int):
@@ -378,6 +395,39 @@ class Engine:
         st = A.SgNodeState()
         _check(lib().sg_read_node(self.h, res, now, C.byref(st)))
         return A.node_state_to_numpy(st)
+
+    # ---- the global inbound node, Constants.ENTRY_NODE (sg_track_inbound)
+    def track_inbound(self, on: bool = True):
+        """Count every EntryType.IN entry and exit on the global inbound node as StatisticSlot does.  Off by default;
+        turning it on is accepted only before the first batch (SentinelError SG_ESTATE afterwards), off at any time."""
+        _check(_inbound("sg_track_inbound")(self.h, 1 if on else 0))
+
+    def read_inbound_node(self, now: int = 0) -> dict:
+        """The node's windows and thread count, as read_node gives a ClusterNode's (SG_ESTATE if never tracked)."""
+        st = A.SgNodeState()
+        _check(_inbound("sg_read_inbound_node")(self.h, int(now), C.byref(st)))
+        return A.node_state_to_numpy(st)
+
+    def inbound_metrics(self, now: int) -> dict:
+        """What SystemRuleManager / SystemStatusListener read of the node at now (sg_inbound_metrics); a read-back."""
+        out = (C.c_double * 9)()
+        k = _inbound("sg_inbound_metrics")(self.h, int(now), out, 9)
+        if k != 9:
+            raise SentinelError(A.SG_ESTATE, (lib().sg_last_error() or b"").decode(errors="replace"))
+        names = ("pass_qps", "block_qps", "success_qps", "exception_qps", "total_qps", "avg_rt", "min_rt",
+                 "max_success_qps", "cur_thread_num")
+        return {names[i]: float(out[i]) for i in range(k)}
+
+    def inbound_last(self):
+        """The inbound pass of the last collected batch: [0] workgroups that left a partial, [1] records visited,
+        [2] updates counted (diagnostics export sgx_inbound_last; drains the pipeline first)."""
+        fn = lib().sgx_inbound_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        out = np.zeros(3, dtype=np.uint64)
+        if fn(self.h, out.ctypes.data, 3) != 3:
+            raise SentinelError(A.SG_ESTATE, "sgx_inbound_last failed (the inbound node was never tracked)")
+        return [int(v) for v in out]
 
     def snapshot(self, now: int, cap: int = 1 << 16) -> np.ndarray:
         out = np.zeros(cap, dtype=A.METRIC_NODE_DTYPE)

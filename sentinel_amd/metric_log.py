@@ -16,9 +16,12 @@ Differences, each deliberate:
   * the writer's clock is injectable (`now_ms`), because replay runs on event time; the
     reference seeds `lastSecond` from System.currentTimeMillis() (MetricWriter.java:104-105);
   * within one timestamp, nodes follow resource-id order (the reference iterates a HashMap of
-    ClusterNodes, MetricTimerListener.java:42 -- an order no caller relies on);
-  * the `__total_inbound_traffic__` row (Constants.ENTRY_NODE) is not produced: the global
-    ENTRY_NODE belongs to SystemSlot, which is out of scope.
+    ClusterNodes, MetricTimerListener.java:42 -- an order no caller relies on).
+
+The `__total_inbound_traffic__` row (Constants.ENTRY_NODE, MetricTimerListener.java:48) is written
+when the engine tracks the global inbound node (`Engine.track_inbound`): the snapshot then carries
+its rows under `RES_TOTAL_INBOUND`, the highest resource id, so the row comes last within its
+timestamp -- where MetricTimerListener.aggregate puts it.
 """
 from __future__ import annotations
 
@@ -31,6 +34,8 @@ from functools import cmp_to_key
 from typing import Dict, Iterable, List, Optional
 
 import numpy as np
+
+from ._abi import RES_TOTAL_INBOUND, TOTAL_IN_RESOURCE_NAME
 
 METRIC_FILE = "metrics.log"
 METRIC_FILE_INDEX_SUFFIX = ".idx"
@@ -248,7 +253,9 @@ class MetricTimerListener:
         snap = snap[np.lexsort((snap["res_id"], snap["timestamp"]))]
         maps: Dict[int, List[MetricNode]] = {}
         for r in snap:
-            node = MetricNode(int(r["timestamp"]), self.names.get(int(r["res_id"]), str(int(r["res_id"]))),
+            rid = int(r["res_id"])
+            name = TOTAL_IN_RESOURCE_NAME if rid == RES_TOTAL_INBOUND else self.names.get(rid, str(rid))
+            node = MetricNode(int(r["timestamp"]), name,
                               int(r["pass_qps"]), int(r["block_qps"]), int(r["success_qps"]),
                               int(r["exception_qps"]), int(r["rt"]), int(r["occupied_pass_qps"]))
             maps.setdefault(node.timestamp, []).append(node)
