@@ -567,6 +567,52 @@ int sg_cluster_set_namespace_connected(sg_engine* e, const char* ns, int32_t con
 int sg_cluster_namespace_qps(sg_engine* e, const char* ns, int64_t now_ms, double* current_qps,
                              double* max_allowed_qps);
 
+/* Cluster metrics of the token server: what cluster/server/metricList answers, one ClusterMetricNode a flowId
+ * (csrv/flow/statistic/ClusterMetricNodeGenerator.java:39-105, metric/ClusterMetric.java:53-72,
+ * metric/ClusterParamMetric.java:91-133, csrv/server/command/handler/FetchClusterMetricCommandHandler.java).
+ * Rows: the cluster flow rules' flowIds ascending (kind SG_CM_FLOW: pass_qps / block_qps = getAvg(PASS) /
+ * getAvg(BLOCK) at now_ms), then the cluster param rules' flowIds ascending (kind SG_CM_PARAM: the top_n values of
+ * largest window sum > 0 with top_qps = sum / (windowIntervalMs / 1000.0), ordered by the 64-bit sum descending and
+ * among equal sums by the key ascending, unsigned).  A flow without traffic has a row of zeros.  ns NULL or "":
+ * every flow; otherwise the flows of that namespace only (an unassigned flowId belongs to "default"; an
+ * unregistered ns: SG_ENOTFOUND).  top_n outside 1..SG_CLUSTER_TOP_MAX: SG_EINVAL (the reference asks for 5).
+ * out is host memory; up to cap rows are written and *n receives the number of rows there are.
+ * A read-back: no bucket is created or reset, no stamp moves and no slot is claimed, so every later request is
+ * decided as it would have been without the call.  The reset that the reference's getAvg / getTopValues apply
+ * through currentWindow() is applied to a copy: with w = interval / sampleCount, i = (now / w) % sampleCount and
+ * ws = now - now % w, bucket i counts as empty if its start is < ws (a FLOW metric's emptied copy of an existing
+ * bucket starts with the pending occupy transfer, PASS += the occupied pass count), a bucket never created or with a
+ * start >= ws is taken as it is, and then every bucket with now - start > interval is left out.  A value's sum adds
+ * its counts of the buckets that survive this and whose stamp equals the flow's.  The reference's cap of 4,000
+ * values per bucket map is not applied.  The table scan and the per-flow selection run on the device, on the
+ * engine's stream; the first call allocates their scratch, sized by the value table's capacity, and keeps it. */
+#define SG_CLUSTER_TOP_MAX 8
+enum { SG_CM_FLOW = 0, SG_CM_PARAM = 1 };
+typedef struct sg_cluster_metric {      /* ClusterMetricNode */
+    int64_t  timestamp;                 /* now_ms */
+    int64_t  flow_id;
+    uint32_t res_id;                    /* the rule's resource */
+    uint32_t kind;                      /* SG_CM_FLOW / SG_CM_PARAM */
+    double   pass_qps, block_qps;       /* FLOW: getAvg(PASS), getAvg(BLOCK); PARAM: 0 */
+    int64_t  rt;                        /* always 0: the reference never sets it */
+    uint32_t n_top, reserved;           /* PARAM: entries used below; FLOW: 0 */
+    uint64_t top_key[SG_CLUSTER_TOP_MAX];
+    double   top_qps[SG_CLUSTER_TOP_MAX];
+} sg_cluster_metric;
+int sg_cluster_metrics(sg_engine* e, const char* ns, int64_t now_ms, uint32_t top_n, sg_cluster_metric* out,
+                       uint64_t cap, uint64_t* n);
+
+/* The value behind a parameter key, the inverse of sg_param_key / sg_param_intern: class_type receives the class
+ * name ("java.lang.String", "int", "long", "double", "float", "byte", "short", "boolean", "char"), value the
+ * value's text, both NUL-terminated; returns the text's length (>= 0).  The kinds whose key holds the value (int,
+ * long within +-2^59, float, byte, short, boolean, char) are decoded from the key; a hashed kind (String, double,
+ * a long outside +-2^59) is looked up in the engine's dictionary (callable from any thread) and returns
+ * SG_ENOTFOUND when no entry owns the key, as for a key the pure function made.  A negative long in range and a
+ * hashed long share their key space: the dictionary is asked first.  A buffer too small: SG_EINVAL.  The key sweep
+ * keeps the keys of claimed (flowId, value) slots, so a key that the metrics call returns resolves. */
+int sg_param_key_value(sg_engine* e, uint64_t key, char* class_type, size_t class_cap, char* value,
+                       size_t value_cap);
+
 /* Node read-back for parity tests: the ClusterNode of res_id. */
 int sg_read_node(sg_engine* e, uint32_t res_id, int64_t now_ms, sg_node_state* out);
 

@@ -244,6 +244,24 @@ final class GpuEngine {
         return out;
     }
 
+    /** The ClusterMetricNodes of ns (null: every flow) at now with the topN hottest values of every param flow
+     *  (sg_cluster_metrics): SG_CLUSTER_METRIC rows, flow rules by flowId, then param rules by flowId. */
+    MemorySegment clusterMetrics(String ns, long now, int topN, Arena into, int cap) {
+        synchronized (nativeLock) {
+            MemorySegment rows = into.allocate(SentinelGpu.SG_CLUSTER_METRIC, Math.max(1, cap));
+            MemorySegment n = into.allocate(JAVA_LONG);
+            MemorySegment name = ns == null ? MemorySegment.NULL : into.allocateFrom(ns);
+            try {
+                SentinelGpu.check((int)SentinelGpu.CLUSTER_METRICS.invokeExact(handle, name, now, topN, rows, (long)cap, n));
+            } catch (RuntimeException ex) {
+                throw ex;
+            } catch (Throwable t) {
+                throw new IllegalStateException(t);
+            }
+            return rows.asSlice(0, Math.min(cap, n.get(JAVA_LONG, 0)) * SentinelGpu.SG_CLUSTER_METRIC.byteSize());
+        }
+    }
+
     // ---- events
     /** Enqueue an ENTRY and park until the batcher has its decision word. */
     int decide(Op op) {

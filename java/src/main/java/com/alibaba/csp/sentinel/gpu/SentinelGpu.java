@@ -182,6 +182,21 @@ final class SentinelGpu {
         JAVA_LONG.withName("value_off")
     ).withName("sg_param_token_req");
 
+    /** ClusterMetricNode (sg_cluster_metrics): SG_CLUSTER_TOP_MAX = 8 top values a param flow. */
+    static final StructLayout SG_CLUSTER_METRIC = MemoryLayout.structLayout(
+        JAVA_LONG.withName("timestamp"),
+        JAVA_LONG.withName("flow_id"),
+        JAVA_INT.withName("res_id"),
+        JAVA_INT.withName("kind"),
+        JAVA_DOUBLE.withName("pass_qps"),
+        JAVA_DOUBLE.withName("block_qps"),
+        JAVA_LONG.withName("rt"),
+        JAVA_INT.withName("n_top"),
+        JAVA_INT.withName("reserved"),
+        MemoryLayout.sequenceLayout(8, JAVA_LONG).withName("top_key"),
+        MemoryLayout.sequenceLayout(8, JAVA_DOUBLE).withName("top_qps")
+    ).withName("sg_cluster_metric");
+
     // ---- downcalls (every export of sentinel_gpu.h)
     private static final Linker LINKER = Linker.nativeLinker();
     private static final SymbolLookup LIB = SymbolLookup.libraryLookup(
@@ -245,6 +260,13 @@ final class SentinelGpu {
         rc(ADDRESS, ADDRESS, JAVA_INT));
     static final MethodHandle CLUSTER_NAMESPACE_QPS = fn("sg_cluster_namespace_qps",
         rc(ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS));
+    /** cluster/server/metricList: (engine, ns or NULL, now, topN, sg_cluster_metric* out, cap, long* n) /
+     *  the value behind a key: (engine, key, char* classType, classCap, char* value, valueCap) -> text length. */
+    static final MethodHandle CLUSTER_METRICS = fn("sg_cluster_metrics",
+        rc(ADDRESS, ADDRESS, JAVA_LONG, JAVA_INT, ADDRESS, JAVA_LONG, ADDRESS));
+    static final MethodHandle PARAM_KEY_VALUE = fn("sg_param_key_value",
+        rc(ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG));
+    static final int CLUSTER_TOP_MAX = 8;
     static final MethodHandle READ_NODE =fn("sg_read_node", rc(ADDRESS, JAVA_INT, JAVA_LONG, ADDRESS));
     /** The global inbound node (Constants.ENTRY_NODE on the device): (engine, on) / (engine, now, sg_node_state* out) /
      *  (engine, now, double* out, cap) -> values written (passQps, blockQps, successQps, exceptionQps, totalQps,

@@ -240,6 +240,46 @@ class SgTokenResult(C.Structure):
     ]
 
 
+CLUSTER_TOP_MAX = 8
+CM_FLOW, CM_PARAM = 0, 1
+
+
+class SgClusterMetric(C.Structure):
+    """sg_cluster_metric: a ClusterMetricNode (sg_cluster_metrics)."""
+    _fields_ = [
+        ("timestamp", C.c_int64),
+        ("flow_id", C.c_int64),
+        ("res_id", C.c_uint32),
+        ("kind", C.c_uint32),
+        ("pass_qps", C.c_double),
+        ("block_qps", C.c_double),
+        ("rt", C.c_int64),
+        ("n_top", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("top_key", C.c_uint64 * CLUSTER_TOP_MAX),
+        ("top_qps", C.c_double * CLUSTER_TOP_MAX),
+    ]
+
+
+CLUSTER_METRIC_DTYPE = np.dtype(
+    [
+        ("timestamp", "<i8"),
+        ("flow_id", "<i8"),
+        ("res_id", "<u4"),
+        ("kind", "<u4"),
+        ("pass_qps", "<f8"),
+        ("block_qps", "<f8"),
+        ("rt", "<i8"),
+        ("n_top", "<u4"),
+        ("reserved", "<u4"),
+        ("top_key", "<u8", (CLUSTER_TOP_MAX,)),
+        ("top_qps", "<f8", (CLUSTER_TOP_MAX,)),
+    ],
+    align=True,
+)
+assert CLUSTER_METRIC_DTYPE.itemsize == C.sizeof(SgClusterMetric) == 184
+
+
 EVENT_DTYPE = np.dtype(
     [
         ("ts", "<i8"),

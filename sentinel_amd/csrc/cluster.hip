@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "chain.h"
+#include "cmwin.h"
 #include "ptok.h"
 #include "pvtab.h"
 
@@ -182,7 +183,7 @@ __device__ int64_t cm_sum(CMetric& M, int64_t now, int ev) {
     int64_t s = 0;
     for (int i = 0; i < M.f->n; ++i) {
         const CBkt& w = M.b[i];
-        if (w.ws < 0 || now - w.ws > M.f->interval) continue;
+        if (CM_SKIPPED(w.ws, now, M.f->interval)) continue;
         s += w.c[ev];
     }
     return s;

@@ -221,6 +221,19 @@ hipError_t launch_ptok_vp(const uint32_t* skeys, const uint32_t* svals, uint64_t
                           hipStream_t st);
 hipError_t launch_pv_rehash(const PVal* src, uint64_t n_src, const PFlow* flows, uint32_t nflows, PVal* dst,
                             uint32_t dmask, uint32_t* out, hipStream_t st);
+// cmetrics.hip
+uint32_t cm_chunk();
+hipError_t launch_cm_rows(const CFlow* cflows, uint32_t ncf, const CBkt* bkts, const PFlow* pflows, uint32_t npf,
+                          int64_t now, uint32_t* mask, sg_cluster_metric* rows, sg_cluster_metric* prows,
+                          hipStream_t st);
+hipError_t launch_cm_scan(const PVal* tab, uint64_t n_slots, const PFlow* flows, uint32_t nflows, const uint32_t* mask,
+                          uint32_t* cflow, uint32_t* cidx, int64_t* csum, uint64_t* ckey, uint32_t cap, uint32_t* cnt,
+                          hipStream_t st);
+hipError_t launch_cm_select(const uint32_t* skeys, const uint32_t* svals, uint32_t n, const PFlow* flows, uint32_t nflows,
+                            const int64_t* csum, const uint64_t* ckey, uint32_t top_n, uint32_t* bounds, uint32_t* nch,
+                            uint32_t* coff, uint32_t* part, int64_t* psum, uint64_t* pkey, sg_cluster_metric* prows,
+                            hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
+                            hipEvent_t* ev, hipStream_t st);
 // keysweep.hip
 hipError_t launch_keysweep(const PMap* pmap, uint32_t nm, const PBucket* pbkt, uint64_t pool_nb, const uint64_t* pbm,
                            uint64_t bm_words, const uint64_t* key_ring, uint64_t ring_n, const PVal* pvtab,
@@ -822,6 +835,20 @@ struct sg_engine {
     uint64_t ks_sweeps = 0, ks_last[4] = {0, 0, 0, 0};  // last sweep: candidates, held on the device, dropped, us
     double ks_scan_ms[3] = {0, 0, 0};             // ... and its scans: maps, key ring, token server values
     uint64_t pbm_words = 0;                       // words of d_pbm
+    // cluster metrics (cmetrics.hip): nothing of this exists before the first sg_cluster_metrics.  The rows
+    // (cluster flows, then param flows, by flow index), the param flows' bucket masks and chunk tables, and, sized by
+    // the value table's capacity, the candidate list, its sort pairs and the partial lists
+    std::unordered_map<int64_t, std::string> cres, pres;  // flowId -> the rule's resource name
+    sg_cluster_metric* d_cm_rows = nullptr;
+    uint32_t *d_cm_mask = nullptr, *d_cm_bounds = nullptr, *d_cm_nch = nullptr, *d_cm_coff = nullptr;
+    uint64_t cm_flow_cap = 0;                     // flows d_cm_rows .. d_cm_coff are sized for
+    uint32_t *d_cm_k0 = nullptr, *d_cm_v0 = nullptr, *d_cm_k1 = nullptr, *d_cm_v1 = nullptr, *d_cm_hist = nullptr,
+             *d_cm_part = nullptr, *d_cm_cnt = nullptr;
+    int64_t *d_cm_sum = nullptr, *d_cm_psum = nullptr;
+    uint64_t *d_cm_key = nullptr, *d_cm_pkey = nullptr;
+    uint64_t cm_cand_cap = 0, cm_chunk_cap = 0;
+    hipEvent_t cm_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double cm_last[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // sgx_cluster_metrics_last
     // snapshot scratch
     uint32_t *d_snap_cnt = nullptr, *d_snap_off = nullptr;
     sg_metric_node* d_snap_out = nullptr;
@@ -1682,6 +1709,8 @@ extern "C" int sgx_param_compact(sg_engine* e) {
 }
 
 static void free_pv(sg_engine* e);
+static void cm_free_flows(sg_engine* e);
+static void cm_free_cands(sg_engine* e);
 
 int sg_engine_destroy(sg_engine* e) {
     if (!e) return SG_OK;
@@ -1709,6 +1738,10 @@ int sg_engine_destroy(sg_engine* e) {
     for (auto& v : e->ks_ev) if (v) (void)hipEventDestroy(v);
     dfree(e->d_pvcnt); dfree(e->d_pvspare); dfree(e->d_ptst); dfree(e->d_ptserial); dfree(e->d_ptdedup);
     for (auto& v : e->pv_ev) if (v) (void)hipEventDestroy(v);
+    cm_free_flows(e);
+    cm_free_cands(e);
+    dfree(e->d_cm_cnt);
+    for (auto& v : e->cm_ev) if (v) (void)hipEventDestroy(v);
     for (auto& s : e->evset)
         for (auto& v : s) if (v) (void)hipEventDestroy(v);
     for (auto& B : e->slot) if (B.h_head) (void)hipHostFree(B.h_head);
@@ -1931,6 +1964,8 @@ static int rebuild_cluster(sg_engine* e, const sg_flow_rule* rules, uint32_t n) 
         nmap[fid] = (uint32_t)nf.size();
         nf.push_back(f);
     }
+    e->cres.clear();
+    for (int64_t fid : order) e->cres[fid] = sv(rule_of[fid]->resource);
     uint32_t cap = 16;
     while (cap < 2 * nf.size() + 2) cap <<= 1;
     std::vector<CSlot> tab(cap);
@@ -2205,6 +2240,8 @@ static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const
         nmap[fid] = (uint32_t)nf.size();
         nf.push_back(f);
     }
+    std::unordered_map<int64_t, std::string> nres;
+    for (int64_t fid : order) nres[fid] = sv(rules[rule_of[fid]].resource);
     const uint32_t cap_v = e->d_pvtab ? e->pv_mask + 1 : 1u << e->pv_log2;
     const bool need_v = !nf.empty() || e->d_pvtab;  // no table until a cluster param rule exists
     std::vector<PVal> vt(need_v ? cap_v : 0);
@@ -2256,6 +2293,7 @@ static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const
     e->pftab_mask = cap - 1;
     e->pflows = std::move(nf);
     e->pmap = std::move(nmap);
+    e->pres = std::move(nres);
     return SG_OK;
 }
 
@@ -3985,6 +4023,212 @@ int sg_cluster_namespace_qps(sg_engine* e, const char* ns, int64_t now_ms, doubl
     if (current_qps) *current_qps = (double)sum / (NS_INTERVAL / 1000.0);
     if (max_allowed_qps) *max_allowed_qps = e->ns_limit[id];
     return SG_OK;
+}
+
+// ---- cluster metrics (cmetrics.hip): ClusterMetricNodeGenerator over every flowId, a read-back
+static void cm_free_flows(sg_engine* e) {
+    dfree(e->d_cm_rows); dfree(e->d_cm_mask); dfree(e->d_cm_bounds); dfree(e->d_cm_nch); dfree(e->d_cm_coff);
+    e->cm_flow_cap = 0;
+}
+static void cm_free_cands(sg_engine* e) {
+    dfree(e->d_cm_k0); dfree(e->d_cm_v0); dfree(e->d_cm_k1); dfree(e->d_cm_v1); dfree(e->d_cm_hist); dfree(e->d_cm_part);
+    dfree(e->d_cm_sum); dfree(e->d_cm_key); dfree(e->d_cm_psum); dfree(e->d_cm_pkey);
+    e->cm_cand_cap = e->cm_chunk_cap = 0;
+}
+// The scratch of a call over ncf + npf flows and a value table of `slots` slots (0: no table).  A slot is a
+// candidate only if it is claimed, and the capacity policy keeps the claimed slots at half of the table at most
+// (pvtab.h); the scan checks the bound all the same.
+static int cm_ensure(sg_engine* e, uint64_t nflows, uint64_t npf, uint64_t slots) {
+    if (!e->d_cm_cnt) HIPCHK(hipMalloc(&e->d_cm_cnt, 8));
+    for (auto& v : e->cm_ev)
+        if (!v) HIPCHK(hipEventCreate(&v));
+    if (nflows > e->cm_flow_cap) {
+        cm_free_flows(e);
+        const uint64_t c = std::max<uint64_t>(nflows, 1u << 10);
+        HIPCHK(hipMalloc(&e->d_cm_rows, c * sizeof(sg_cluster_metric)));
+        HIPCHK(hipMalloc(&e->d_cm_mask, c * 4));
+        HIPCHK(hipMalloc(&e->d_cm_bounds, (c + 2) * 4));
+        HIPCHK(hipMalloc(&e->d_cm_nch, (c + 2) * 4));
+        HIPCHK(hipMalloc(&e->d_cm_coff, (c + 2) * 4));
+        e->cm_flow_cap = c;
+    }
+    const uint64_t cands = slots / 2 + 1;
+    const uint64_t chunks = cands / cm_chunk() + e->cm_flow_cap + 1;
+    if (slots && (cands > e->cm_cand_cap || chunks > e->cm_chunk_cap)) {
+        cm_free_cands(e);
+        const uint64_t nblocks = (cands + radix_tile() - 1) / radix_tile();
+        HIPCHK(hipMalloc(&e->d_cm_k0, cands * 4));
+        HIPCHK(hipMalloc(&e->d_cm_v0, cands * 4));
+        HIPCHK(hipMalloc(&e->d_cm_k1, cands * 4));
+        HIPCHK(hipMalloc(&e->d_cm_v1, cands * 4));
+        HIPCHK(hipMalloc(&e->d_cm_sum, cands * 8));
+        HIPCHK(hipMalloc(&e->d_cm_key, cands * 8));
+        HIPCHK(hipMalloc(&e->d_cm_hist, nblocks * 256 * 4));
+        HIPCHK(hipMalloc(&e->d_cm_part, (nblocks + e->cm_flow_cap + 1024) * 4));  // (a scan's partials: one a tile)
+        HIPCHK(hipMalloc(&e->d_cm_psum, chunks * SG_CLUSTER_TOP_MAX * 8));
+        HIPCHK(hipMalloc(&e->d_cm_pkey, chunks * SG_CLUSTER_TOP_MAX * 8));
+        e->cm_cand_cap = cands;
+        e->cm_chunk_cap = chunks;
+    }
+    (void)npf;
+    return SG_OK;
+}
+
+int sg_cluster_metrics(sg_engine* e, const char* ns, int64_t now_ms, uint32_t top_n, sg_cluster_metric* out,
+                       uint64_t cap, uint64_t* n) {
+    if (!e || !n || (cap && !out)) return fail(SG_EINVAL, "null argument");
+    if (top_n < 1 || top_n > SG_CLUSTER_TOP_MAX) return fail(SG_EINVAL, "top_n must lie in 1..SG_CLUSTER_TOP_MAX");
+    if (now_ms < 0) return fail(SG_EINVAL, "negative time");
+    bool all = !ns || !ns[0];
+    uint32_t ns_id = 0;
+    if (!all) {
+        auto it = e->ns_of.find(ns);
+        if (it == e->ns_of.end()) return fail(SG_ENOTFOUND, "namespace is not registered");
+        ns_id = it->second;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = drain(e)) return rc;
+    const auto t_begin = std::chrono::steady_clock::now();
+    const uint32_t ncf = (uint32_t)e->cflows.size(), npf = (uint32_t)e->pflows.size();
+    for (double& v : e->cm_last) v = 0;
+    e->cm_last[2] = cm_chunk();
+    *n = 0;
+    if (!ncf && !npf) return SG_OK;
+    const uint64_t slots = npf && e->d_pvtab ? (uint64_t)e->pv_mask + 1 : 0;
+    if (int rc = cm_ensure(e, (uint64_t)ncf + npf, npf, slots)) return rc;
+    hipStream_t st = e->stream;
+    sg_cluster_metric* prows = e->d_cm_rows + ncf;
+    HIPCHK(hipEventRecord(e->cm_ev[0], st));
+    HIPCHK(launch_cm_rows(e->d_cflow, ncf, e->d_cbkt, e->d_pflow, npf, now_ms, e->d_cm_mask, e->d_cm_rows, prows, st));
+    HIPCHK(hipEventRecord(e->cm_ev[1], st));
+    uint32_t ncand = 0;
+    if (slots) {
+        HIPCHK(launch_cm_scan(e->d_pvtab, slots, e->d_pflow, npf, e->d_cm_mask, e->d_cm_k0, e->d_cm_v0, e->d_cm_sum,
+                              e->d_cm_key, (uint32_t)e->cm_cand_cap, e->d_cm_cnt, st));
+        HIPCHK(hipMemcpyAsync(&ncand, e->d_cm_cnt, 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipEventRecord(e->cm_ev[2], st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ncand > e->cm_cand_cap) return fail(SG_EDEVICE, "cluster metrics: more candidates than half of the value table");
+    for (int k = 3; k < 6; ++k) HIPCHK(hipEventRecord(e->cm_ev[k], st));  // (a call without candidates: empty stages)
+    if (ncand) {
+        uint32_t *kin = e->d_cm_k0, *vin = e->d_cm_v0, *kout = e->d_cm_k1, *vout = e->d_cm_v1;
+        int bits = 1;
+        while (bits < 32 && (1ull << bits) < npf) ++bits;  // keys 0 .. npf - 1
+        const int passes = (bits + 7) / 8;
+        const uint32_t nblocks = (uint32_t)(((uint64_t)ncand + radix_tile() - 1) / radix_tile());
+        for (int p = 0; p < passes; ++p) {
+            HIPCHK(launch_radix_hist(kin, ncand, p * 8, e->d_cm_hist, nblocks, st));
+            HIPCHK(launch_scan(e->d_cm_hist, e->d_cm_hist, (uint64_t)nblocks * 256, e->d_cm_part, nullptr, st));
+            HIPCHK(launch_radix_scatter(kin, vin, ncand, p * 8, e->d_cm_hist, nblocks, kout, vout, nullptr, st));
+            std::swap(kin, kout);
+            std::swap(vin, vout);
+        }
+        HIPCHK(launch_cm_select(kin, vin, ncand, e->d_pflow, npf, e->d_cm_sum, e->d_cm_key, top_n, e->d_cm_bounds,
+                                e->d_cm_nch, e->d_cm_coff, e->d_cm_part, e->d_cm_psum, e->d_cm_pkey, prows, launch_scan,
+                                e->cm_ev + 3, st));
+        HIPCHK(hipEventRecord(e->cm_ev[5], st));
+    }
+    std::vector<sg_cluster_metric> rows((size_t)ncf + npf);
+    uint32_t nchunks = 0;
+    if (ncand) HIPCHK(hipMemcpyAsync(&nchunks, e->d_cm_coff + npf, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rows.data(), e->d_cm_rows, rows.size() * sizeof(sg_cluster_metric), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // the rows in the defined order: flow rules by flowId, then param rules by flowId, of the namespace asked for
+    auto emit = [&](const std::unordered_map<int64_t, uint32_t>& idx, const std::unordered_map<int64_t, std::string>& res,
+                    uint32_t base) {
+        std::vector<int64_t> ids;
+        for (auto& kv : idx)
+            if (all || ns_index(e, kv.first) == ns_id) ids.push_back(kv.first);
+        std::sort(ids.begin(), ids.end());
+        for (int64_t fid : ids) {
+            sg_cluster_metric r = rows[base + idx.at(fid)];
+            auto rn = res.find(fid);
+            if (rn != res.end()) {
+                auto id = e->ids.find(rn->second);
+                if (id != e->ids.end()) r.res_id = id->second;
+            }
+            if (*n < cap) out[*n] = r;
+            ++*n;
+        }
+    };
+    emit(e->cmap, e->cres, 0);
+    emit(e->pmap, e->pres, ncf);
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < 5; ++k)
+        if (hipEventElapsedTime(&ms[k], e->cm_ev[k], e->cm_ev[k + 1]) != hipSuccess) ms[k] = 0;
+    (void)hipGetLastError();
+    e->cm_last[0] = ncand;
+    e->cm_last[1] = nchunks;
+    e->cm_last[3] = (double)slots;
+    for (int k = 0; k < 5; ++k) e->cm_last[4 + k] = ms[k];
+    e->cm_last[9] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return SG_OK;
+}
+
+// diagnostics export: the last sg_cluster_metrics call: [0] candidates (claimed slots with a sum > 0), [1] chunks the
+// select stage cut them into, [2] candidates a chunk holds at most, [3] value table slots scanned, then the device
+// times in ms (HIP events) of [4] the rows and masks, [5] the scan, [6] the grouping (sort, bounds, chunk table),
+// [7] the select, [8] the merge, and [9] the call's wall time in ms.  Returns the values written.
+extern "C" int sgx_cluster_metrics_last(sg_engine* e, double* out, int cap) {
+    if (!e || !out) return 0;
+    int k = 0;
+    for (; k < 10 && k < cap; ++k) out[k] = e->cm_last[k];
+    return k;
+}
+
+int sg_param_key_value(sg_engine* e, uint64_t key, char* class_type, size_t class_cap, char* value, size_t value_cap) {
+    if (!e || !class_type || !value) return fail(SG_EINVAL, "null argument");
+    const uint32_t tag = (uint32_t)(key >> 60);
+    const uint64_t v = key & pk::KEY_MASK;
+    const char* ct = nullptr;
+    std::string text;
+    char buf[64];
+    auto num = [&](const char* fmt, auto x) { std::snprintf(buf, sizeof(buf), fmt, x); text = buf; };
+    std::string canon;
+    const bool maybe_entry = tag == 1 || tag == 4 || (tag == 3 && (v & pk::LONG_HASHED));
+    const bool found = maybe_entry && e->pkeys.value_of(key, canon);
+    switch (tag) {
+    case 1:
+        if (!found) return fail(SG_ENOTFOUND, "no dictionary entry owns this key");
+        ct = "java.lang.String";
+        text = canon.substr(1);
+        break;
+    case 2: ct = "int"; num("%d", (int)(int32_t)(uint32_t)v); break;
+    case 3: {
+        ct = "long";
+        long long x;
+        if (found && canon.size() == 9) std::memcpy(&x, canon.data() + 1, 8);
+        else x = (long long)(v << 4) >> 4;  // the 60-bit two's complement value
+        num("%lld", x);
+        break;
+    }
+    case 4: {
+        if (!found || canon.size() != 9) return fail(SG_ENOTFOUND, "no dictionary entry owns this key");
+        ct = "double";
+        double d;
+        std::memcpy(&d, canon.data() + 1, 8);
+        num("%.17g", d);
+        break;
+    }
+    case 5: {
+        ct = "float";
+        const uint32_t u = (uint32_t)v;
+        float f;
+        std::memcpy(&f, &u, 4);
+        num("%.9g", (double)f);
+        break;
+    }
+    case 6: ct = "byte"; num("%d", (int)(int8_t)(uint8_t)v); break;
+    case 7: ct = "short"; num("%d", (int)(int16_t)(uint16_t)v); break;
+    case 8: ct = "boolean"; text = v ? "true" : "false"; break;
+    case 9: ct = "char"; text.assign(1, (char)(unsigned char)v); break;
+    default: return fail(SG_ENOTFOUND, "not a parameter value key");
+    }
+    if (std::strlen(ct) + 1 > class_cap || text.size() + 1 > value_cap) return fail(SG_EINVAL, "buffer too small");
+    std::memcpy(class_type, ct, std::strlen(ct) + 1);
+    std::memcpy(value, text.c_str(), text.size() + 1);
+    return (int)text.size();
 }
 
 // Batched DefaultTokenService.requestToken (see cluster.hip for the device steps).

@@ -172,6 +172,15 @@ class Dict {
         by_key_[k] = ins.first->second.get();
         return k;
     }
+    // The inverse: the canonical bytes (tag byte, then the text or the 8 raw bytes) of the entry that owns key.
+    // False when no entry does, as for a pure key that was never interned.  Does not touch the entry.
+    bool value_of(uint64_t key, std::string& canon) const {
+        std::shared_lock<std::shared_mutex> lk(mu_);
+        auto it = by_key_.find(key);
+        if (it == by_key_.end()) return false;
+        canon = *it->second->value;
+        return true;
+    }
     void unpin(uint64_t key) {
         std::unique_lock<std::shared_mutex> lk(mu_);
         auto it = by_key_.find(key);

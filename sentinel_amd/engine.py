@@ -29,6 +29,7 @@ EXPORTS = (
     "sg_cluster_namespace_qps", "sg_load_authority_rules", "sg_param_intern", "sg_param_intern_batch",
     "sg_param_keys_sweep", "sg_param_keys_stats", "sg_cluster_param_table_stats",
     "sg_track_inbound", "sg_read_inbound_node", "sg_inbound_metrics",
+    "sg_cluster_metrics", "sg_param_key_value",
 )
 
 
@@ -96,6 +97,21 @@ def _inbound(name):
     fn = getattr(lib(), name)
     if fn.argtypes is None:
         fn.argtypes = _INBOUND_ARGS[name]()
+    return fn
+
+
+# the cluster metrics' entry points, bound on first use for the same reason
+_CMETRICS_ARGS = {
+    "sg_cluster_metrics": lambda: [C.c_void_p, C.c_char_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                   C.POINTER(C.c_uint64)],
+    "sg_param_key_value": lambda: [C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t],
+}
+
+
+def _cmetrics(name):
+    fn = getattr(lib(), name)
+    if fn.argtypes is None:
+        fn.argtypes = _CMETRICS_ARGS[name]()
     return fn
 
 
@@ -468,6 +484,65 @@ class Engine:
         cur, lim = C.c_double(), C.c_double()
         _check(lib().sg_cluster_namespace_qps(self.h, name.encode(), int(now), C.byref(cur), C.byref(lim)))
         return cur.value, lim.value
+
+    # ---- cluster/server/metricList: a ClusterMetricNode per flowId (csrv/flow/statistic/ClusterMetricNodeGenerator.java)
+    def cluster_metrics(self, now: int, ns=None, top: int = 5, cap: int = None) -> np.ndarray:
+        """sg_cluster_metrics at now: A.CLUSTER_METRIC_DTYPE rows, the cluster flow rules' flowIds ascending, then the
+        cluster param rules' with their `top` hottest values (sum descending, key ascending).  ns: a registered
+        namespace's flows only (None: every flow).  A read-back: no later decision depends on the call.  cap: rows
+        to return at most (None: all)."""
+        n = C.c_uint64()
+        fn = _cmetrics("sg_cluster_metrics")
+        nsb = None if ns is None else str(ns).encode()
+        want = 4096 if cap is None else int(cap)
+        out = np.zeros(max(1, want), dtype=A.CLUSTER_METRIC_DTYPE)
+        _check(fn(self.h, nsb, int(now), int(top), out.ctypes.data, want, C.byref(n)))
+        if cap is None and n.value > want:  # (more flows than the first buffer holds: once more, with room for all)
+            want = n.value
+            out = np.zeros(want, dtype=A.CLUSTER_METRIC_DTYPE)
+            _check(fn(self.h, nsb, int(now), int(top), out.ctypes.data, want, C.byref(n)))
+        return out[: min(want, n.value)]
+
+    def cluster_metrics_count(self, now: int, ns=None, top: int = 5) -> int:
+        """The number of rows cluster_metrics would return (sg_cluster_metrics with cap 0)."""
+        n = C.c_uint64()
+        _check(_cmetrics("sg_cluster_metrics")(self.h, None if ns is None else str(ns).encode(), int(now), int(top),
+                                               None, 0, C.byref(n)))
+        return n.value
+
+    def cluster_metrics_last(self) -> dict:
+        """The last cluster_metrics call (diagnostics export sgx_cluster_metrics_last): candidates, chunks, the chunk
+        size, table slots scanned, per-stage device times in ms (HIP events) and the call's wall time in ms."""
+        fn = lib().sgx_cluster_metrics_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
+        out = (C.c_double * 10)()
+        if fn(self.h, out, 10) != 10:
+            raise SentinelError(A.SG_EDEVICE, "sgx_cluster_metrics_last failed")
+        names = ("candidates", "chunks", "chunk_size", "slots", "rows_ms", "scan_ms", "group_ms", "select_ms",
+                 "merge_ms", "wall_ms")
+        d = {names[i]: float(out[i]) for i in range(10)}
+        for k in names[:4]:
+            d[k] = int(d[k])
+        return d
+
+    def param_key_value(self, key: int):
+        """sg_param_key_value: (class_type, text) of the value behind a parameter key, or None when the key is of a
+        hashed kind (String, double, a long outside +-2^59) and no dictionary entry owns it."""
+        fn = _cmetrics("sg_param_key_value")
+        ct = C.create_string_buffer(32)
+        cap = 256
+        while True:
+            val = C.create_string_buffer(cap)
+            rc = fn(self.h, int(key), ct, len(ct), val, cap)
+            if rc >= 0:
+                return ct.value.decode(), val.raw[:rc].decode(errors="replace")
+            if rc == A.SG_ENOTFOUND:
+                return None
+            if rc == A.SG_EINVAL and cap < (1 << 24):
+                cap *= 16
+                continue
+            _check(rc)
 
     def cluster_request_array(self, reqs: np.ndarray) -> np.ndarray:
         """reqs: A.TOKEN_REQ_DTYPE array (time-ordered) -> A.TOKEN_RES_DTYPE array."""

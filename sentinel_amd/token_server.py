@@ -291,6 +291,7 @@ class TokenServer:
         self.batches: List[int] = []      # sizes of the device calls (observability)
         self.submitted: List[tuple] = []  # (xids, requests, results) of every device call, in order
         self.errors: List[str] = []       # device-call failures answered with FAIL (observability)
+        self.resource_names: Dict[int, str] = {}  # res_id -> resource name, for metric_list (the caller fills it)
 
     async def start(self, host: str = "127.0.0.1", port: int = DEFAULT_CLUSTER_SERVER_PORT):
         self._server = await asyncio.start_server(self._serve, host, port)
@@ -313,6 +314,41 @@ class TokenServer:
         rehashes ...; observability, next to `sweeps`); {} for a service without it."""
         fn = getattr(self.service, "cluster_param_table_stats", None)
         return fn() if fn is not None else {}
+
+    def metric_list(self, namespace: str, now: Optional[int] = None, top: int = 5) -> Dict[str, List[dict]]:
+        """What cluster/server/metricList answers (csrv/server/command/handler/FetchClusterMetricCommandHandler.java
+        over ClusterMetricNodeGenerator.generateCurrentNodeMap(namespace)): resource name -> the ClusterMetricNodes of
+        the namespace's flowIds at `now` (default: the clock), each a dict with timestamp, resourceName, flowId,
+        passQps, blockQps, rt and topParams (value text -> QPS of the `top` hottest values of a param rule; a key
+        whose value the service cannot name appears as "#%016x").  An empty namespace raises ValueError, as the
+        handler fails; a namespace without flows gives {}.  Resource names come from `self.resource_names`
+        (res_id -> name; a missing one appears as "#<res_id>").  One `cluster_metrics` call on the service: a
+        read-back, made between ticks like every device call.  Serving the HTTP command itself is out of scope."""
+        if not namespace or not str(namespace).strip():
+            raise ValueError("namespace cannot be empty")
+        now = self.clock() if now is None else int(now)
+        if self.ns_qps is not None:  # the device knows the namespaces
+            if namespace != DEFAULT_NAMESPACE and namespace not in self.ns_qps:
+                return {}
+            rows = self.service.cluster_metrics(now, ns=namespace, top=top)
+        else:
+            rows = [r for r in self.service.cluster_metrics(now, top=top)
+                    if self.flow_ns.get(int(r["flow_id"]), DEFAULT_NAMESPACE) == namespace]
+        names = getattr(self, "resource_names", None) or {}
+        lookup = getattr(self.service, "param_key_value", None)
+        out: Dict[str, List[dict]] = {}
+        for r in rows:
+            res = names.get(int(r["res_id"]), "#%d" % int(r["res_id"]))
+            tops = {}
+            for k in range(int(r["n_top"])):
+                key = int(r["top_key"][k])
+                hit = lookup(key) if lookup is not None else None
+                tops[hit[1] if hit is not None else "#%016x" % key] = float(r["top_qps"][k])
+            out.setdefault(res, []).append({
+                "timestamp": int(r["timestamp"]), "resourceName": res, "flowId": int(r["flow_id"]),
+                "passQps": float(r["pass_qps"]), "blockQps": float(r["block_qps"]), "rt": int(r["rt"]),
+                "topParams": tops})
+        return out
 
     def _update_connected(self, namespace: str):
         n = self.conns.count(namespace)
