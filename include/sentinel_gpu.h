@@ -502,6 +502,32 @@ int sg_inbound_metrics(sg_engine* e, int64_t now_ms, double* out, int cap);
 int sg_cluster_set_connected_count(sg_engine* e, int64_t flow_id, int32_t connected);
 int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n, sg_token_result* out);
 
+/* Embedded token server: ClusterStateManager's server state (core/cluster/ClusterStateManager.java).  Off (the
+ * default), a cluster_mode flow rule is decided as in a process that is neither token client nor token server
+ * (FlowRuleChecker.passClusterCheck, core/slots/block/flow/FlowRuleChecker.java:126-143): without
+ * cluster_fallback_to_local it limits nothing.  On, this engine is the TokenService of its own decision path
+ * (pickClusterService -> EmbeddedClusterTokenServerProvider.getServer(), :155-163): every ENTRY that reaches FlowSlot
+ * on a resource whose flow rule is a cluster rule -- it has a chain, Constants.ON is set, it is not in a
+ * NullContext, and neither SG_F_BLOCKED_UPSTREAM nor the authority rule blocked it -- issues
+ * requestToken(flowId, count, prioritized) at its own ts, and obeys the answer (applyTokenResult, :165-187):
+ *   OK            FlowSlot passes, DegradeSlot follows
+ *   SHOULD_WAIT   passes after waitInMs: SG_PASS with the wait in bits 16.. (0 if a breaker then blocks); only a
+ *                 prioritized entry can get it
+ *   BLOCKED       SG_BLOCK_FLOW with the rule's slot; StatisticSlot counts the block
+ *   TOO_MANY_REQUEST, BAD_REQUEST (count 0), FAIL, NO_RULE_EXISTS   fallbackToLocalOrPass: the entry passes
+ * Tokens are consumed whatever DegradeSlot decides.  The token state is the one sg_cluster_request_tokens serves:
+ * calls and batches take effect in call order, a batch's requests in event order; a rejected batch consumes nothing.
+ * Supported shape: the cluster rule is the only flow rule of its resource, QPS grade, limitApp "default", strategy
+ * DIRECT, without cluster_fallback_to_local, with a flowId no other loaded flow rule uses; the resource has no
+ * param rules and is in no STRATEGY_RELATE component; degrade and authority rules are free.  While the mode is on,
+ * a flow- or param-rule load that would leave a cluster flow rule outside this shape returns SG_ENOTSUP, and so
+ * does switching the mode on over such rules: sg_last_error names the rule and nothing has changed.  Cluster-mode
+ * param rules keep their behaviour (no TokenService on the decision path) in either mode.  The call drains the
+ * pipeline and compiles the programs again; node, breaker and token state stay.  A batch that holds events of such
+ * resources is handed to the decide stage before the next batch is grouped (it gives up the pipeline's overlap),
+ * and synchronous batches of at most 256 events take the batched path while such a rule is loaded. */
+int sg_cluster_embedded(sg_engine* e, int32_t on);
+
 /* Batched TokenService.requestParamToken (core/cluster/TokenService.java:37-46,
  * csrv/flow/DefaultTokenService.java:50-61 -> csrv/flow/ClusterParamFlowChecker.java:42-88).
  * Rules come from the param rules loaded with cluster_mode=1 (the ClusterParamFlowRuleManager role,

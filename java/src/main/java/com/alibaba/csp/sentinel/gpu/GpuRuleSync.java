@@ -12,6 +12,7 @@ import java.util.List;
 import java.util.Map;
 import java.util.Set;
 
+import com.alibaba.csp.sentinel.cluster.ClusterStateManager;
 import com.alibaba.csp.sentinel.property.PropertyListener;
 import com.alibaba.csp.sentinel.property.SentinelProperty;
 import com.alibaba.csp.sentinel.slots.block.RuleConstant;
@@ -66,6 +67,7 @@ final class GpuRuleSync {
         } catch (ReflectiveOperationException ex) {
             throw new IllegalStateException("sentinel_gpu: rule managers without currentProperty", ex);
         }
+        setEmbedded(ClusterStateManager.isServer());
         rehook();
     }
 
@@ -141,12 +143,46 @@ final class GpuRuleSync {
         }
     }
 
+    /**
+     * ClusterStateManager.isServer() to the engine: in embedded mode FlowRuleChecker.pickClusterService returns
+     * EmbeddedClusterTokenServerProvider.getServer() (FlowRuleChecker.java:155-163), so the engine, which replaces
+     * FlowSlot, asks its own token server for every entry on a cluster rule.  The state is read, not listened to (its
+     * property is private to the manager): when the engine attaches (no rule is loaded yet, so the switch cannot be
+     * refused) and around every flow-rule load, see loadFlow.
+     */
+    static void setEmbedded(boolean on) {
+        synchronized (engine.nativeLock) {
+            try {
+                SentinelGpu.check((int)SentinelGpu.CLUSTER_EMBEDDED.invokeExact(engine.handle, on ? 1 : 0));
+            } catch (RuntimeException ex) {
+                throw ex;
+            } catch (Throwable t) {
+                throw new IllegalStateException("sentinel_gpu: applying the cluster server state failed", t);
+            }
+        }
+    }
+
+    /**
+     * The incoming list is checked against the state the process is in now, never the list on the device against it:
+     * a process that is not the server switches the mode off first (that cannot fail) and then loads; a server loads
+     * first -- with the mode already on, the engine refuses a list outside the supported shape and keeps the old one,
+     * a list that removes the offending rules is accepted -- and switches the mode on afterwards.  That switch is
+     * refused (SG_ENOTSUP, thrown here) only if the list just loaded holds a cluster rule outside the shape: the new
+     * rules are then on the device, decided as without a TokenService, and the next load tries again.
+     */
     static void loadFlow(List<FlowRule> rules) {
+        final boolean server = ClusterStateManager.isServer();
+        if (!server) {
+            setEmbedded(false);
+        }
         try (Arena a = Arena.ofConfined()) {
             push(SentinelGpu.LOAD_FLOW_RULES, NativeRules.flow(a, rules), rules.size(), "flow");
         }
         // FlowRuleManager's own grouping and FlowRuleComparator order (FlowRuleUtil.java:89-158)
         flowByResource = FlowRuleUtil.buildFlowRuleMap(rules);
+        if (server) {
+            setEmbedded(true);
+        }
     }
 
     static void loadDegrade(List<DegradeRule> rules) {

@@ -273,6 +273,10 @@ final class SentinelGpu {
      *  avgRt, minRt, maxSuccessQps, curThreadNum). */
     static final MethodHandle TRACK_INBOUND = fn("sg_track_inbound", rc(ADDRESS, JAVA_INT));
     static final MethodHandle READ_INBOUND_NODE = fn("sg_read_inbound_node", rc(ADDRESS, JAVA_LONG, ADDRESS));
+    /** Embedded token server, ClusterStateManager's server state: (engine, on).  On, the flow rules' cluster rules are
+     *  decided on the decision path by the engine's own token server; SG_ENOTSUP (nothing changed) if a loaded cluster
+     *  flow rule lies outside the supported shape. */
+    static final MethodHandle CLUSTER_EMBEDDED = fn("sg_cluster_embedded", rc(ADDRESS, JAVA_INT));
     static final MethodHandle INBOUND_METRICS = fn("sg_inbound_metrics", rc(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT));
     /** res_id of the inbound node's sg_metric_node rows, and the name they are logged under. */
     static final int RES_TOTAL_INBOUND = 0xFFFFFFFF;

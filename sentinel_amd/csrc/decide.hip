@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "authority.h"
+#include "embedded.h"
 #include "chain.h"
 #include "aux.h"
 #include "pmap.h"
@@ -173,7 +174,8 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
                                                  const uint32_t* __restrict__ nhotseg, uint32_t* __restrict__ need_hot,
                                                  uint32_t* __restrict__ need_blk, const uint32_t* __restrict__ bmax,
                                                  uint32_t skip_min, uint32_t* __restrict__ nmark,
-                                                 uint32_t* __restrict__ ubc) {
+                                                 uint32_t* __restrict__ ubc, uint32_t* __restrict__ embc,
+                                                 uint32_t max_res) {
     __shared__ uint32_t cnt[N_BINS];
     for (uint32_t b = threadIdx.x; b < N_BINS; b += blockDim.x) cnt[b] = 0;
     __syncthreads();
@@ -188,8 +190,11 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
         sg = segs[s];
         const uint32_t end = (s + 1 < m) ? segs[s + 1].start : (uint32_t)n;
         sg.len = end - sg.start;
-        const Prog p = prog[sg.res];
-        const uint32_t pm = prio[sg.res];
+        // (a res_id >= max_resources sorts into a segment of its own before the host has read BF_BAD_RES and refused
+        // the batch: nothing is read for it -- an empty program, no marks)
+        const bool okr = sg.res < max_res;
+        const Prog p = okr ? prog[sg.res] : Prog{};
+        const uint32_t pm = okr ? prio[sg.res] : 0u;
         // decided one lane per segment whatever the length: a live borrow ring (PM_PRIO), events only k_lane takes
         // (PM_LANE), origin / context nodes the rules read (PX_ORIGIN / PX_CHAIN: k_lane<16> keeps them inline)
         const bool lane_base = (pm & (PM_PRIO | PM_LANE)) != 0 || ((pm & PM_AUX) && (p.multi & (PX_ORIGIN | PX_CHAIN)));
@@ -199,7 +204,10 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
         // its segment where they would take it without the mark -- by the lane bins' own limit, not k_lite's longer one
         // nor the head owner's shorter one: neither kernel is taught the class -- with the pre-blocked ENTRYs as blocks
         // whose words k_ublk_words writes (SEG_UBLK).  Everything else with the mark keeps the lane bins (lane_entry).
-        const bool ub = (pm & PM_UBLK) != 0;
+        // An XF_EMB resource (embedded token server) is the same class whatever its events are: the token call of the
+        // batch may refuse any of its ENTRYs, and a refused one is a pre-decided block
+        const bool pmub = (pm & PM_UBLK) != 0, emb = (p.xf & XF_EMB) != 0;
+        const bool ub = pmub || emb;
         const bool ubs = ub && !lane_base && !force_lane && !(p.pflags & PF_SERIAL) && (p.n_param == 0 || mixp) &&
                          !p.multi && sg.len > lane_max;
         const bool lane_only = lane_base || (ub && !ubs);
@@ -239,7 +247,8 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
         else {
             int lb = 31 - __clz(sg.len | 1);
             if (lb > (int)LANE_BINS - 1) lb = LANE_BINS - 1;
-            bin = (lite ? BIN_LITE : (nr <= 4 && !inline_aux) ? BIN_LANE : BIN_LANE16) + (LANE_BINS - 1 - lb);
+            // (an XF_EMB segment on k_lane<16> whatever its rule count: the only lane kernel that reads DevState.emb)
+            bin = (lite ? BIN_LITE : (nr <= 4 && !inline_aux && !emb) ? BIN_LANE : BIN_LANE16) + (LANE_BINS - 1 - lb);
         }
         // k_lane<16> keeps a PM_AUX resource's nodes inline; on every other owner the post-pass does
         const bool auxp = aux && (pm & PM_AUX) && !(bin >= BIN_LANE16 && bin < BIN_LANE16 + LANE_BINS);
@@ -278,7 +287,13 @@ __global__ __launch_bounds__(256) void k_seg_bin(Seg* __restrict__ segs, const u
             }
         }
         // (ubs implies coop, and not PF_PQ -- param rules without XF_MIX: one of J1 / J4 / J8 / J16)
-        if (ub && ubc) atomicAdd(&ubc[ubs ? 0 : 1], 1u);  // (diagnostics and the host's launch of k_ublk_words)
+        if (pmub && ubc) atomicAdd(&ubc[ubs ? 0 : 1], 1u);  // (diagnostics and the host's launch of k_ublk_words)
+        // embc: [0] events of XF_EMB segments -- an upper bound of the batch's token requests, which the host reads
+        // with the head: 0 means the batch takes the usual path -- [1] such segments in cooperative bins, [2] in lane bins
+        if (emb && embc) {
+            atomicAdd(&embc[0], sg.len);
+            atomicAdd(&embc[ubs ? 1 : 2], 1u);
+        }
         const uint32_t rank = atomicAdd(&cnt[bin], 1u);
         sg.bin = bin | (auxp ? SEG_AUXP : 0u) | (tabs ? SEG_TABS : 0u) | (ubs ? SEG_UBLK : 0u) | (rank << SEG_RANK_SHIFT);
         segs[s] = sg;
@@ -526,11 +541,12 @@ __global__ __launch_bounds__(256) void k_fill(const Span* __restrict__ spans, co
 // is left at once.  cnt: the words written (diagnostics).
 __global__ __launch_bounds__(256) void k_ublk_words(SEv* __restrict__ recs, const Seg* __restrict__ segs,
                                                     const uint32_t* __restrict__ order, uint32_t m,
-                                                    uint32_t* __restrict__ dec, uint32_t* __restrict__ cnt) {
+                                                    uint32_t* __restrict__ dec, uint32_t* __restrict__ cnt,
+                                                    const uint32_t* __restrict__ emb, uint32_t* __restrict__ ecnt) {
     if (blockIdx.x >= m) return;
     const Seg sg = segs[order[blockIdx.x]];
     if (!(sg.bin & SEG_UBLK)) return;
-    uint32_t nw = 0;
+    uint32_t nw = 0, ne = 0;
     for (uint32_t p = threadIdx.x; p < sg.len; p += blockDim.x) {
         const uint32_t w = reinterpret_cast<const uint4*>(recs)[sg.start + p].w;
         const uint32_t fl = (w >> 8) & 0xFFu;
@@ -538,9 +554,19 @@ __global__ __launch_bounds__(256) void k_ublk_words(SEv* __restrict__ recs, cons
             recs[sg.start + p].flags = (uint8_t)(fl | RF_PBLK);
             dec[sg.start + p] = mk_dec((fl & SG_F_BLOCKED_UPSTREAM) ? ST_BLOCK_UPSTREAM : ST_BLOCK_AUTHORITY, 0, 0);
             ++nw;
+        } else if (emb && (w & 0xFFu) == SG_EV_ENTRY && !(fl & (RF_UBLK | RF_PBLK))) {
+            // embedded token server: the token call answered BLOCKED for this ENTRY (its side word is the final word,
+            // embedded.h emb_word); the same class to the owner.  A pre-blocked ENTRY made no request: its word is 0
+            const uint32_t ew = emb[sg.start + p];
+            if (emb_word_blocks(ew)) {
+                recs[sg.start + p].flags = (uint8_t)(fl | RF_PBLK);
+                dec[sg.start + p] = ew & 0xFFFFu;
+                ++ne;
+            }
         }
     }
     if (nw) atomicAdd(cnt, nw);
+    if (ne) atomicAdd(ecnt, ne);
 }
 
 // CtSph.lookProcessChain (core/CtSph.java:206-227): resources touched by this batch with neither a
@@ -1061,12 +1087,21 @@ __device__ __forceinline__ uint32_t upstream_status(const DevState& S, uint32_t 
 template <int NRMAX, bool MULTI = false>
 __device__ __forceinline__ uint32_t lane_entry(Node& N, const Ctx& C, const DevState& S, const DevCfg& cfg,
                                                const Prog& pg, RState (&rs)[NRMAX], uint32_t res, int64_t t, int cnt,
-                                               uint32_t fl, const EvX& x, uint32_t* bflags, PmLane* L = nullptr) {
+                                               uint32_t fl, const EvX& x, uint32_t* bflags, PmLane* L = nullptr,
+                                               uint32_t epos = 0xFFFFFFFFu) {
     const DRule* rules = S.rules + pg.rule_off;
     const int np = pg.n_param, nfl = np + pg.n_flow, nr = nfl + pg.n_degrade;
     const bool aux = NRMAX >= 16;  // origin nodes / DefaultNodes (PM_AUX resources and PX_* rules are k_lane<16>'s)
     uint32_t status = ST_PASS, slot = 0;
-    int64_t wait = 0;
+    // ew: the embedded token server's word for this ENTRY (embedded.h emb_word), read at the ENTRY's sorted position epos
+    // for an XF_EMB program in a batch that made token requests (S.emb), else 0; such a program has no flow stage.  It is
+    // FlowSlot's verdict, honoured where the first flow rule would be -- after the upstream slots,
+    // before DegradeSlot.  A SHOULD_WAIT answer's wait counts as a rate limiter's (FlowRuleChecker.java:165-187)
+    uint32_t ew = 0;
+    // (k_lane<16> only: k_seg_bin sends an XF_EMB segment of the lane bins there, so k_lane<4> carries none of this)
+    if (NRMAX >= 16 && (pg.xf & XF_EMB) && S.emb != nullptr && epos != 0xFFFFFFFFu) ew = S.emb[epos];
+    const bool eblk = emb_word_blocks(ew);
+    int64_t wait = eblk ? 0 : (int64_t)(ew >> 16);
     // SystemSlot (the caller's flag), then AuthoritySlot: evaluated once (a pure function of the event), honoured
     // after the param rules and before the first flow or degrade rule
     const uint32_t up = upstream_status(S, res, fl, x.origin);
@@ -1122,11 +1157,13 @@ __device__ __forceinline__ uint32_t lane_entry(Node& N, const Ctx& C, const DevS
                 else wait += w;
             } else {  // DegradeRuleManager.checkDegrade (DegradeRuleManager.java:72-85)
                 if (s == np && up != ST_PASS) { status = up; slot = 0; continue; }  // (no flow rule: still before DegradeSlot)
+                if (s == np && eblk) { status = ST_BLOCK_FLOW; slot = (ew >> 8) & 0xFFu; continue; }
                 if (!degrade_pass(N, C, deg_param(r), rs[s], t)) { status = ST_BLOCK_DEGRADE; slot = r.slot; }
             }
         }
     }
     if (status == ST_PASS && nr == np && up != ST_PASS) { status = up; slot = 0; }  // (no flow or degrade rule)
+    if (status == ST_PASS && nr == np && eblk) { status = ST_BLOCK_FLOW; slot = (ew >> 8) & 0xFFu; }
     // StatisticSlot.entry (StatisticSlot.java:54-133): DefaultNode -> ClusterNode, origin node
     const int what = status == ST_PASS ? 1 : status == ST_PASS_WAIT ? 2 : 0;
     if (aux) {  // ClusterBuilderSlot's origin node, NodeSelectorSlot's DefaultNode: counted whatever the rules
@@ -1308,7 +1345,7 @@ __device__ __forceinline__ void lane_seg(const SEv* __restrict__ recs, const sg_
         uint32_t d = mk_dec(ST_NOT_ENTRY, 0, 0);
         if (r.kind == SG_EV_ENTRY) {
             if (!chain) d = mk_dec(ST_NO_CHECK, 0, 0);
-            else d = lane_entry<NRMAX>(N, C, S, cfg, pg, rs, res, t, r.cnt, r.flags, x, bflags, LP);
+            else d = lane_entry<NRMAX>(N, C, S, cfg, pg, rs, res, t, r.cnt, r.flags, x, bflags, LP, sg.start + j);
             if (j < 64 && st_passed(d & 0xFF)) pm |= 1ull << j;
             LPROF(ktb)
         } else {
@@ -4193,13 +4230,14 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
                           const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
-                          uint32_t skip_min, uint32_t* nmark, uint32_t* ubc, hipStream_t st) {
+                          uint32_t skip_min, uint32_t* nmark, uint32_t* ubc, uint32_t* embc, uint32_t max_res,
+                          hipStream_t st) {
     const uint32_t nblk = (mb + 255) / 256;
     if (!nblk) return hipSuccess;
     hipLaunchKernelGGL(k_seg_bin, dim3(nblk), dim3(256), 0, st, segs, mp, n, prog, prio, lane_max, lite_max, j1_max, j4_max,
                        force_lane,
                        blkcnt, nblk, pq_ok, pq_wide, aux, ashort, along, amulti, mixc, mix, mix_cap, mixlen, mix_wide,
-                       head_min, hot_tab, nhot, nhotseg, need_hot, need_blk, bmax, skip_min, nmark, ubc);
+                       head_min, hot_tab, nhot, nhotseg, need_hot, need_blk, bmax, skip_min, nmark, ubc, embc, max_res);
     return hipGetLastError();
 }
 // off = exclusive scan of blkcnt (bin-major); writes the per-bin offsets to bin_off[0..N_BINS]
@@ -4229,9 +4267,9 @@ hipError_t launch_fill(const Span* spans, const uint32_t* nspan, uint32_t cap, c
 }
 // order[0 .. m): the dispatch list of the cooperative bins (BIN_J16 .. BIN_J8, contiguous)
 hipError_t launch_ublk_words(SEv* recs, const Seg* segs, const uint32_t* order, uint32_t m, uint32_t* dec,
-                             uint32_t* cnt, hipStream_t st) {
+                             uint32_t* cnt, const uint32_t* emb, uint32_t* ecnt, hipStream_t st) {
     if (!m) return hipSuccess;
-    hipLaunchKernelGGL(k_ublk_words, dim3(m), dim3(256), 0, st, recs, segs, order, m, dec, cnt);
+    hipLaunchKernelGGL(k_ublk_words, dim3(m), dim3(256), 0, st, recs, segs, order, m, dec, cnt, emb, ecnt);
     return hipGetLastError();
 }
 hipError_t launch_resolve(const uint32_t* prev, uint32_t np, const uint8_t* ring, SEv* recs, const uint32_t* vals,

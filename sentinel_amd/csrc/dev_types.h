@@ -124,7 +124,11 @@ enum : uint16_t {
                          // checks by pvalue.hip's passes, k_pq then folding the statistics only (SG_PV_PQ)
     XF_HEADT = 16,       // the only rule is one THREAD-grade DefaultController flow rule on the ClusterNode (DIRECT,
                          // limitApp default): its J16 / J4 segments take the event-driven head owner (head.hip)
-    XF_HEADR = 32        // ... one QPS RateLimiter (or WarmUpRateLimiter of count > 0) flow rule likewise
+    XF_HEADR = 32,       // ... one QPS RateLimiter (or WarmUpRateLimiter of count > 0) flow rule likewise
+    XF_EMB = 64          // embedded token server (embedded.h): the resource's only flow rule is a cluster rule whose
+                         // tokens this engine counts.  The program has no flow stage; the batch's token call decides
+                         // the rule ahead of the owners, and an ENTRY it refused is a pre-decided block: the
+                         // cooperative owners take the segment as a SEG_UBLK one, a lane reads DevState.emb
 };
 enum : uint32_t {
     PX_MULTI = 1,        // representative of a STRATEGY_RELATE component (its members share one segment)
@@ -502,6 +506,10 @@ struct DevState {
     // unless authority rules are loaded
     const AuthDesc* auth;
     const uint32_t* auth_ids;
+    // embedded token server: per sorted position the word the token call left for an ENTRY of an XF_EMB resource
+    // (embedded.h emb_word: a BLOCKED answer's final word, a SHOULD_WAIT answer's wait, else 0); null unless the
+    // batch made a token request
+    const uint32_t* emb;
 };
 
 enum : uint32_t { BF_PRIORITIZED = 1,

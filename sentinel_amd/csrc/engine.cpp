@@ -24,6 +24,7 @@
 #include "../../include/sentinel_gpu.h"
 #include "authority.h"
 #include "dev_types.h"
+#include "embedded.h"
 #include "pkeys.h"
 #include "pmap.h"  // (pm_buckets: sg_param_thread_count)
 #include "pvtab.h"
@@ -99,7 +100,8 @@ hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n
                           uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
                           uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
                           const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
-                          uint32_t skip_min, uint32_t* nmark, uint32_t* ubc, hipStream_t st);
+                          uint32_t skip_min, uint32_t* nmark, uint32_t* ubc, uint32_t* embc, uint32_t max_res,
+                          hipStream_t st);
 // aux.hip
 hipError_t launch_aux(const SEv* recs, const Seg* segs, const uint32_t* aux, const uint32_t* ashort,
                       const uint64_t* along, uint64_t* apiece, const uint64_t* amulti, const DevState& S, const DevCfg& cfg,
@@ -160,7 +162,17 @@ hipError_t launch_fill(const Span* spans, const uint32_t* nspan, uint32_t cap, c
 hipError_t launch_resolve(const uint32_t* prev, uint32_t np, const uint8_t* ring, SEv* recs, const uint32_t* vals,
                           const sg_event_ext* ext, hipStream_t st);
 hipError_t launch_ublk_words(SEv* recs, const Seg* segs, const uint32_t* order, uint32_t m, uint32_t* dec,
-                             uint32_t* cnt, hipStream_t st);
+                             uint32_t* cnt, const uint32_t* emb, uint32_t* ecnt, hipStream_t st);
+hipError_t launch_emb_count(const sg_event* ev, const sg_event_ext* ext, uint64_t n, uint32_t max_res, uint32_t max_ctx,
+                            const Prog* prog, const NodeInfo* info, const AuthDesc* auth, const uint32_t* auth_ids,
+                            int32_t switch_on, uint32_t* cnt, uint32_t* part, uint32_t* total, hipStream_t st);
+hipError_t launch_emb_scatter(const sg_event* ev, const sg_event_ext* ext, uint64_t n, uint32_t max_res, uint32_t max_ctx,
+                              const Prog* prog, const NodeInfo* info, const AuthDesc* auth, const uint32_t* auth_ids,
+                              int32_t switch_on, const uint32_t* off, const int64_t* flow_of, uint32_t cap,
+                              sg_token_req* req, uint32_t* idx, hipStream_t st);
+hipError_t launch_emb_answers(const sg_token_result* res, const uint32_t* idx, uint32_t nreq, const uint32_t* pos_of,
+                              const uint32_t* words, const uint32_t* P, uint32_t nhot, uint64_t n, uint32_t* side,
+                              uint32_t* stat, hipStream_t st);
 hipError_t launch_post_w(const uint32_t* words, const uint32_t* P, uint32_t nhot, const uint32_t* dec, uint64_t n,
                          uint64_t gbase, uint8_t* ring, uint64_t ring_mask, uint32_t* out, hipStream_t st);
 hipError_t launch_post(const uint32_t* pos_of, const uint32_t* dec, uint64_t n, uint64_t gbase, uint8_t* ring,
@@ -524,6 +536,8 @@ template <class T> void dfree(T*& p) {
 
 // =====================================================================================
 #define TMAP_KEY (1ull << 63)  // pmap_key of a thread-count map: TMAP_KEY | res << 8 | paramIdx
+constexpr int EMB_LAST_WORDS = 12;  // sgx_embedded_last: [0] requests, [1..7] answers (EMB_A_*), [8] words written ahead,
+                                    // [9] XF_EMB segments in cooperative bins, [10] in lane bins, [11] in the late lane pass
 struct sg_engine {
     sg_config cfg;
     int device = 0;
@@ -597,6 +611,8 @@ struct sg_engine {
         uint32_t nhot = 0;             // ... with these hot ids (its words and P in d_flag / d_pos)
         uint32_t hot_marked = 0;       // ... of which k_seg_bin marked this many for the side tables (d_bsmall[73])
         uint32_t ublk_coop = 0, ublk_lane = 0;  // PM_UBLK segments in cooperative / lane bins (d_bsmall[74], [75])
+        uint32_t emb_ub = 0, emb_coop = 0, emb_lane = 0;  // XF_EMB segments: their events (an upper bound of the batch's
+                                                          // token requests), those in cooperative / lane bins ([83..85])
         Seg* d_segs = nullptr;
         uint64_t* d_cand = nullptr;
         uint32_t* d_bsmall = nullptr;  // [0] bflags [1] nseg [2] ncand [3] nprev [4..5] t0 [8..8+N_BINS] bin offsets
@@ -616,6 +632,8 @@ struct sg_engine {
         hipEvent_t* ev = nullptr;      // the batch's event set (evset[]): group start/end, decide start/end, post end
         hipEvent_t last_post = nullptr;  // post end of the last batch decided from this slot: the next group stage to
                                          // fill the slot waits for it on the device
+        hipEvent_t lent = nullptr;       // the slot's arrays were the scratch of the other slot's embedded token call,
+                                         // which ends here on the engine stream: the next group stage waits for it too
         uint32_t* h_head = nullptr;    // pinned: d_bsmall[0..77) as the group stage left it (copied on gstream)
         // What the decide stage needs of the group part's locals: it may run inside the next submit, after
         // e->gbase, e->epoch and the d_* aliases have moved on, so nothing of these is re-read from the engine.
@@ -643,7 +661,7 @@ struct sg_engine {
     hipEvent_t evset[N_SETS][5] = {};
     uint32_t* h_mirror = nullptr;  // pinned, N_SETS x MIRROR_WORDS: d_bsmall[0..121) as the decide stage left it
     uint64_t seq = 0;              // batches handed to the decide stage so far (batch i has set i % N_SETS)
-    struct InFlight { int set; uint32_t hot_marked, ublk_coop, ublk_lane; };
+    struct InFlight { int set; uint32_t hot_marked, ublk_coop, ublk_lane, emb_coop, emb_lane; };
     std::deque<InFlight> inflight;  // handed off, not yet collected (timings, flags), oldest first
     hipStream_t gstream = nullptr;
     std::vector<std::array<double, 4>> tlog;  // per batch [group, decide, post, total] ms, by collect()
@@ -665,6 +683,20 @@ struct sg_engine {
     uint32_t* d_edges = nullptr;
     uint32_t hot_marked_last = 0;  // hot ids marked for the side tables in the last collected batch (sgx_hot_marked)
     uint32_t ublk_last[3] = {0, 0, 0};  // sgx_preblocked_last: PM_UBLK segments in cooperative / lane bins, RF_UBLK words
+    // Embedded token server (embedded.h; ClusterStateManager's server state): emb_on: the mode; emb_n: resources whose
+    // program is XF_EMB (0: every batch takes the usual path); d_emb_flow: [res] the flowId of an XF_EMB resource;
+    // d_emb_side: the side words of the batch being decided (DevState.emb), d_emb_idx: its requests' batch indices,
+    // d_emb_cnt / d_emb_part: the extraction's tile counts and scan partials.  All allocated on first use.
+    bool emb_on = false;
+    uint32_t emb_n = 0;
+    int64_t* d_emb_flow = nullptr;
+    uint32_t *d_emb_side = nullptr, *d_emb_idx = nullptr, *d_emb_cnt = nullptr, *d_emb_part = nullptr;
+    uint64_t emb_cap = 0;
+    hipEvent_t emb_ev[2] = {nullptr, nullptr};  // the end of the token call that borrowed slot [i]'s arrays (BatchSlot.lent)
+    hipEvent_t emb_t[4] = {nullptr, nullptr, nullptr, nullptr};  // around the extraction, the token call and the scatter
+    bool emb_timed = false;            // ... recorded for the batch in flight (one at a time: no overlap)
+    double emb_ms[3] = {0, 0, 0};      // sgx_embedded_ms: their times in the last collected batch that made requests
+    uint64_t emb_last[EMB_LAST_WORDS] = {};  // sgx_embedded_last
     // the global inbound node, Constants.ENTRY_NODE (inbound.hip): allocated by the first sg_track_inbound(1); inb_on:
     // batches are counted on it, inb_ever: it exists (readable after tracking was turned off)
     InbNode* d_inb = nullptr;
@@ -942,7 +974,7 @@ int ensure_batch(sg_engine* e, uint64_t n) {
     return SG_OK;
 }
 
-constexpr uint32_t HEAD_WORDS = 77;     // d_bsmall words the host reads after the group stage
+constexpr uint32_t HEAD_WORDS = 86;     // d_bsmall words the host reads after the group stage
 constexpr uint32_t MIRROR_WORDS = 121;  // ... and after the decide stage ([0] bflags, [119] RF_UBLK words written,
                                         // [120] frozen spans)
 
@@ -982,6 +1014,20 @@ static int collect(sg_engine* e) {
     e->ublk_last[0] = f.ublk_coop;
     e->ublk_last[1] = f.ublk_lane;
     e->ublk_last[2] = mir[119];
+    // the embedded token server's read-back: [100] requests, [101..107] answers by class, [108] words written ahead
+    for (int i = 0; i < 9; ++i) e->emb_last[i] = mir[100 + i];
+    e->emb_last[9] = f.emb_coop;
+    e->emb_last[10] = f.emb_lane;
+    e->emb_last[11] = 0;  // (no late lane pass: rules with cluster_fallback_to_local are refused)
+    if (e->emb_timed && mir[100]) {  // (the batch's events are done: its post end was waited for above)
+        for (int i = 0; i < 3; ++i) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, e->emb_t[i], e->emb_t[i + 1]);
+            e->emb_ms[i] = ms;
+        }
+        (void)hipGetLastError();
+        e->emb_timed = false;
+    }
     // Flags the decide kernels raise (the group stage's own checks return before the decide stage runs):
     // an EXIT/TRACE whose reference names an event that is not an earlier ENTRY of its resource, and a
     // batch starting before the last window a resource already holds (the clock went back).
@@ -1036,6 +1082,37 @@ static uint32_t rule_map_cap(int64_t duration_sec) {
     return (uint32_t)std::min<int64_t>(c, PM_TOTAL_CAP);
 }
 
+// Embedded token server: the supported shape of a cluster flow rule, in one place for the refusals (emb_refuse) and
+// the compile (upload_rules marks XF_EMB exactly where emb_why finds nothing to object to).  A resource holding a
+// cluster-mode flow rule must have that rule as its only flow rule -- QPS grade (flow_valid has dropped a rule without
+// a flowId), limitApp "default", strategy DIRECT, a flowId no other loaded flow rule uses -- no param rules, and no
+// RELATE rule of another resource may name it: then the batch's requests depend on no verdict the batch still has to
+// find.  A rule with cluster_fallback_to_local is outside it too: the local check of a refused request is not built.
+struct EmbShape {
+    std::unordered_map<long long, int> uses;  // flowId -> cluster flow rules naming it
+    std::set<std::string> related;            // resources of a STRATEGY_RELATE pair
+    explicit EmbShape(const std::vector<FlowR>& flows) {
+        for (const FlowR& f : flows) {
+            if (f.r.cluster_mode) ++uses[(long long)f.r.cluster_flow_id];
+            if (f.r.strategy == SG_STRATEGY_RELATE && !f.ref.empty() && f.ref != f.res) { related.insert(f.ref); related.insert(f.res); }
+        }
+    }
+    // why the cluster rule f of resource r lies outside the shape (null: it is eligible)
+    const char* why(const FlowR& f, size_t r, const std::vector<std::vector<int>>& res_flow,
+                    const std::vector<std::vector<int>>& res_par) const {
+        if (r >= res_flow.size() || res_flow[r].size() != 1) return "it is not the only flow rule of its resource";
+        if (f.r.grade != SG_FLOW_GRADE_QPS) return "it is not QPS grade";
+        if (f.la != "default") return "its limitApp is not \"default\"";
+        if (f.r.strategy != SG_STRATEGY_DIRECT) return "its strategy is not DIRECT";
+        auto it = uses.find((long long)f.r.cluster_flow_id);
+        if (it == uses.end() || it->second != 1) return "another flow rule uses its flowId";
+        if (r < res_par.size() && !res_par[r].empty()) return "its resource has param rules";
+        if (related.count(f.res)) return "its resource is in a STRATEGY_RELATE component";
+        if (f.r.cluster_fallback_to_local) return "cluster_fallback_to_local is not decided in embedded mode";
+        return nullptr;
+    }
+};
+
 // Build the device rule program of every resource from the compiled host lists.
 int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool reset_par_state) {
     uint32_t R = e->cfg.max_resources;
@@ -1054,6 +1131,8 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
     }
     size_t nres = e->names.size();
     bool any_mix = false, any_head = false;
+    std::vector<std::pair<uint32_t, int64_t>> emb_res;  // embedded mode: the XF_EMB resources and their flowIds
+    const EmbShape emb_shape(e->flows);                 // ... told by the shape test the refusals use
     std::vector<std::pair<uint32_t, uint32_t>> relate;  // (resource, referenced resource) of RELATE rules
     for (size_t r = 0; r < nres && r < R; ++r) {
         Prog p;
@@ -1265,6 +1344,17 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
                 if (p.xf & (XF_HEADT | XF_HEADR)) any_head = true;
             }
         }
+        // Embedded token server: the resource's only flow rule is a cluster rule this engine counts the tokens of
+        // (emb_refuse has refused every other shape while the mode is on).  The program is what the rule compiles to
+        // without a TokenService -- no flow stage, the breakers as usual -- plus the flag: the batch's token call
+        // decides the rule (decide_enqueue)
+        if (e->emb_on && fl.size() == 1 && p.n_flow == 0) {
+            const FlowR& f = e->flows[fl[0]];
+            if (f.r.cluster_mode && !emb_shape.why(f, r, e->res_flow, e->res_par)) {
+                p.xf |= XF_EMB;
+                emb_res.emplace_back((uint32_t)r, (int64_t)f.r.cluster_flow_id);
+            }
+        }
         // carry controller / breaker state of kinds that were not reloaded
         if (!old_rst.empty()) {
             const Prog& op = old_prog[r];
@@ -1359,6 +1449,13 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
     }
     if (!hot.empty()) HIPCHK(hipMemcpy(e->d_hot, hot.data(), hot.size() * sizeof(DHot), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_prog, prog.data(), R * sizeof(Prog), hipMemcpyHostToDevice));
+    if (!emb_res.empty()) {  // [res] -> flowId, read for XF_EMB resources only
+        if (!e->d_emb_flow) HIPCHK(hipMalloc(&e->d_emb_flow, (uint64_t)R * 8));
+        std::vector<int64_t> flow_of(R, 0);
+        for (const auto& er : emb_res) flow_of[er.first] = er.second;
+        HIPCHK(hipMemcpy(e->d_emb_flow, flow_of.data(), (uint64_t)R * 8, hipMemcpyHostToDevice));
+    }
+    e->emb_n = (uint32_t)emb_res.size();
     e->n_dev_rules = (uint32_t)rules.size();
     e->has_mix = any_mix;
     e->has_head = any_head;
@@ -1399,6 +1496,23 @@ static int check_rule_limits(const sg_engine* e, const std::vector<ParamR>& para
         total += n;
     }
     if (total > e->cfg.max_rules) return fail(SG_ECAPACITY, "compiled rule table exceeds max_rules");
+    return SG_OK;
+}
+
+// What the mode cannot decide, told from the host lists alone, before anything of the engine changes (SG_ENOTSUP names
+// the rule; the caller returns it and nothing has changed).
+static int emb_refuse(const sg_engine* e, const std::vector<FlowR>& flows, const std::vector<std::vector<int>>& res_flow,
+                      const std::vector<std::vector<int>>& res_par) {
+    (void)e;
+    const EmbShape shape(flows);
+    for (size_t r = 0; r < res_flow.size(); ++r)
+        for (int i : res_flow[r]) {
+            const FlowR& f = flows[i];
+            if (!f.r.cluster_mode) continue;
+            if (const char* why = shape.why(f, r, res_flow, res_par))
+                return fail(SG_ENOTSUP, "embedded token server: cluster flow rule " + std::to_string((long long)f.r.cluster_flow_id) +
+                                            " on " + f.res + " is outside the supported shape: " + why);
+        }
     return SG_OK;
 }
 
@@ -1732,6 +1846,11 @@ int sg_engine_destroy(sg_engine* e) {
     dfree(e->d_pflow); dfree(e->d_phot); dfree(e->d_pftab); dfree(e->d_pvtab); dfree(e->d_preq); dfree(e->d_pvals);
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab); dfree(e->d_nslim); dfree(e->d_nslimit); dfree(e->d_nsb); dfree(e->d_borrow); dfree(e->d_keyring);
     dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx); dfree(e->d_tbounds);
+    dfree(e->d_emb_flow); dfree(e->d_emb_side); dfree(e->d_emb_idx); dfree(e->d_emb_cnt); dfree(e->d_emb_part);
+    for (auto& x : e->emb_ev)
+        if (x) (void)hipEventDestroy(x);
+    for (auto& x : e->emb_t)
+        if (x) (void)hipEventDestroy(x);
     dfree(e->d_snap_cnt); dfree(e->d_snap_off); dfree(e->d_snap_out); dfree(e->d_dbg);
     dfree(e->d_inb); dfree(e->d_inbpart);
     dfree(e->d_ks_key); dfree(e->d_ks_idx); dfree(e->d_ks_marks);
@@ -2050,6 +2169,8 @@ int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint
         });
     }
     if (int rc = check_rule_limits(e, e->params, e->res_par, flows, per, e->res_deg)) return rc;
+    if (e->emb_on)
+        if (int rc = emb_refuse(e, flows, per, e->res_par)) return rc;
     // publish
     auto old_flows = std::move(e->flows);
     auto old_per = std::move(e->res_flow);
@@ -2576,6 +2697,8 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
         }
     // the checks first: with SG_ENOTSUP / SG_ECAPACITY neither the cluster rules nor the maps change
     if (int rc = check_rule_limits(e, ps, per, e->flows, e->res_flow, e->res_deg)) return rc;
+    if (e->emb_on)
+        if (int rc = emb_refuse(e, e->flows, e->res_flow, per)) return rc;
     uint64_t need = (rcap.size() + tmaps.size()) * (uint64_t)PM_MIN_NB * PM_BKT;  // (new maps' first regions)
     if (need > (1ull << e->cfg.param_table_log2))
         return fail(SG_ECAPACITY, "hot-parameter maps need " + std::to_string(need) + " slots, param_table_log2 = " +
@@ -2746,6 +2869,10 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
     hipStream_t gs = e->gstream;
     // the slot's last batch is decided and its decisions are out before anything of the slot is overwritten
     if (B.last_post) HIPCHK(hipStreamWaitEvent(gs, B.last_post, 0));
+    if (B.lent) {  // ... and the embedded token call that used the slot's arrays as scratch is through
+        HIPCHK(hipStreamWaitEvent(gs, B.lent, 0));
+        B.lent = nullptr;
+    }
     const sg_event* dev_ev = ev;
     bool host_in = !is_device_ptr(ev);
     bool host_out = !is_device_ptr(out);
@@ -2852,7 +2979,8 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
                               B.d_ashort, B.d_along, B.d_amulti, e->d_bsmall + 6, e->has_mix ? B.d_mix : nullptr,
                               (uint32_t)B.mix_cap, e->d_bsmall + 72, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
                               (e->dbg_flags & HEAD_OFF) ? 0u : e->head_min, e->d_hot_tab, e->nhot, e->d_bsmall + 80, need_hot,
-                              need_blk, bmax, skip_min, e->d_bsmall + 73, e->d_bsmall + 74, gs));
+                              need_blk, bmax, skip_min, e->d_bsmall + 73, e->d_bsmall + 74, e->emb_n ? e->d_bsmall + 83 : nullptr,
+                              R, gs));
         HIPCHK(launch_scan(e->d_blkcnt, e->d_blkcnt, (uint64_t)nblk * N_BINS, e->d_part, nullptr, gs));
         HIPCHK(launch_seg_order(e->d_segs, e->d_bsmall + 1, mb, e->d_blkcnt, e->d_order, e->d_bsmall + 8, gs));
         return SG_OK;
@@ -2946,8 +3074,9 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
                                 e->d_bsmall + 76, gs));
     // [0] bflags [1] nseg [3] nprev [4..5] t0 [6..7] XF_MIX lists [8..8+N_BINS] bin offsets [72] wide XF_MIX events
     // [73] hot ids marked for the side tables [74] PM_UBLK segments in cooperative bins (SEG_UBLK) [75] in lane bins
-    // [76] the next batch's hot ids
-    static_assert(8 + N_BINS + 1 <= 72 && HEAD_WORDS == 77, "head layout");
+    // [76] the next batch's hot ids [77..82] the hot / cold stage's own [83] events of XF_EMB segments [84] XF_EMB
+    // segments in cooperative bins [85] in lane bins
+    static_assert(8 + N_BINS + 1 <= 72 && HEAD_WORDS == 86, "head layout");
     HIPCHK(hipMemcpyAsync(B.h_head, e->d_bsmall, HEAD_WORDS * 4, hipMemcpyDeviceToHost, gs));
     HIPCHK(hipEventRecord(B.ev[1], gs));
     auto& G = B.g;
@@ -2977,6 +3106,9 @@ static int accept_grouped(sg_engine* e, bool drop = false) {
     B.hot_marked = head[73];
     B.ublk_coop = head[74];
     B.ublk_lane = head[75];
+    B.emb_ub = e->emb_n ? head[83] : 0u;
+    B.emb_coop = e->emb_n ? head[84] : 0u;
+    B.emb_lane = e->emb_n ? head[85] : 0u;
     const uint32_t bflags = head[0];
     if (bflags & BF_BAD_RES) return fail(SG_EINVAL, "event res_id >= max_resources");
     if (bflags & BF_BAD_REF)
@@ -2990,7 +3122,7 @@ static int accept_grouped(sg_engine* e, bool drop = false) {
     if (e->has_mix && head[7] && (e->pv_on || e->pvt_on) && head[72]) {
         if (int prc = ensure_pv(e, head[72], head[7])) return prc;
     }
-    e->inflight.push_back({B.g.set, B.hot_marked, B.ublk_coop, B.ublk_lane});
+    e->inflight.push_back({B.g.set, B.hot_marked, B.ublk_coop, B.ublk_lane, B.emb_coop, B.emb_lane});
     ++e->seq;
     e->last = k;
     e->cur = k ^ 1;
@@ -3007,6 +3139,7 @@ static int handoff(sg_engine* e) {
 }
 
 static int decide_enqueue(sg_engine* e, int k);
+static int embedded_tokens(sg_engine* e, int k, uint32_t* nreq_out);
 
 // The decide stage of the accepted batch in slot k.  The batch is counted already (accept_grouped), so a decide
 // stage that could not be enqueued whole -- a device error -- leaves the engine inconsistent: it refuses every later
@@ -3150,6 +3283,13 @@ static int decide_enqueue(sg_engine* e, int k) {
             }
         }
     }
+    // Embedded token server: the batch's token requests, decided by one token call ahead of every owner (after the
+    // chain grants, which the request test reads).  Only a batch that holds events of XF_EMB resources comes here
+    if (B.emb_ub) {
+        uint32_t nreq = 0;
+        if (int erc = embedded_tokens(e, k, &nreq)) return erc;
+        if (nreq) S.emb = e->d_emb_side;
+    }
     // XF_MIX segments of the cooperative bins (and XF_PVPQ ones): their param checks first (the value-parallel pre
     // pass, else k_pq's), the owners then decide the flow / degrade chain on them.  The pre pass runs on
     // bin_stream[1] (whose J4 / J1 wait for it anyway); its extraction and sort touch no map region, so they start
@@ -3191,9 +3331,10 @@ static int decide_enqueue(sg_engine* e, int k) {
                              e->d_dec, e->d_bsmall + 0, ps, pv_ran ? e->d_pvrest + 1 : nullptr, e->d_pvrest));
     // Pre-blocked ENTRYs of the cooperative bins' segments (SEG_UBLK): their words and RF_PBLK after the param pre
     // pass (whose block comes first) and before every owner; launched only in a batch that has such a segment
-    if (head[74])
+    // (and the ENTRYs the embedded token call answered BLOCKED, in a batch that made requests)
+    if (head[74] || (S.emb && B.emb_coop))
         HIPCHK(launch_ublk_words(e->d_recs, e->d_segs, e->d_order + off[BIN_J16], off[BIN_J8 + 1] - off[BIN_J16], e->d_dec,
-                                 e->d_bsmall + 119, ps));
+                                 e->d_bsmall + 119, S.emb, e->d_bsmall + 108, ps));
     HIPCHK(hipEventRecord(e->fork, ps));
     auto lane_bins = [&]() -> int {
         {
@@ -3375,7 +3516,10 @@ static int submit_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
     // short before that compacts on the device itself (launch_pm_grow)
     const unsigned long long pfloor = e->h_pool_next ? e->h_pool_next[PC_FLOOR] : 0;
     const bool compact = e->pool_nb && e->h_pool_next[PC_NEXT] > pfloor + (e->pool_nb - pfloor) / 2;
-    if (!late || compact) {  // the earlier order: the batch two back is collected before its slot is taken again
+    // A grouped batch with events of XF_EMB resources (embedded token server) gives up its overlap: its token call
+    // uses the other slot's arrays as scratch and waits on the host, so its decide stage goes first
+    const bool emb_prev = prev >= 0 && e->slot[prev].emb_ub != 0;
+    if (!late || compact || emb_prev) {  // the earlier order: the batch two back is collected before its slot is taken again
         if (prev >= 0) {
             const int pk = prev;
             prev = -1;
@@ -3532,7 +3676,7 @@ int sg_submit_ex_async(sg_engine* e, const sg_event* ev, const sg_event_ext* ext
 
 int sg_submit_ex(sg_engine* e, const sg_event* ev, const sg_event_ext* ext, uint64_t n, const sg_arg* args,
                  uint64_t n_args, uint32_t* out) {
-    if (e && e->tiny_on && n && n <= tiny_max() && !e->radix_group) {
+    if (e && e->tiny_on && !e->emb_n && n && n <= tiny_max() && !e->radix_group) {
         const int trc = tiny_impl(e, ev, ext, n, args, n_args, out);
         if (trc != TINY_FALLBACK) return trc;
     }
@@ -3590,7 +3734,7 @@ int sg_sync(sg_engine* e) {
 }
 
 int sg_submit(sg_engine* e, const sg_event* ev, uint64_t n, uint32_t* out) {
-    if (e && e->tiny_on && n && n <= tiny_max() && !e->radix_group) {
+    if (e && e->tiny_on && !e->emb_n && n && n <= tiny_max() && !e->radix_group) {
         const int trc = tiny_impl(e, ev, nullptr, n, nullptr, 0, out);
         if (trc != TINY_FALLBACK) return trc;
     }
@@ -4231,13 +4375,10 @@ int sg_param_key_value(sg_engine* e, uint64_t key, char* class_type, size_t clas
     return (int)text.size();
 }
 
-// Batched DefaultTokenService.requestToken (see cluster.hip for the device steps).
-int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n, sg_token_result* out) {
-    if (!e || (n && (!reqs || !out))) return fail(SG_EINVAL, "null argument");
-    if (!n) return SG_OK;
-    if (n > 0x7FFFFFFFull) return fail(SG_EINVAL, "too many token requests in one call");
-    if (int rc = drain(e)) return rc;
-    hipStream_t st = e->stream;
+// Batched DefaultTokenService.requestToken (see cluster.hip for the device steps), in two parts so that the decide
+// stage can issue a batch's own requests (embedded token server): tok_ensure makes room for n requests and the
+// tables a call reads, tok_device decides the n requests already in e->d_treq into e->d_tres.
+static int tok_ensure(sg_engine* e, uint64_t n) {
     int rc = ensure_batch(e, n);  // radix-sort scratch
     if (rc) return rc;
     if (n > e->tcap) {
@@ -4256,9 +4397,14 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
         HIPCHK(hipMemcpy(e->d_ctab, t, sizeof(t), hipMemcpyHostToDevice));
         e->ctab_mask = 15;
     }
+    return SG_OK;
+}
+// The requests are in time order and their tables exist (tok_ensure).  The active batch slot's arrays (activate()) are
+// the call's scratch: no batch may be using them.  The classification's flag is read back on the host, so every
+// earlier kernel of the engine stream is done when this returns; the flows' kernels may still be running.
+static int tok_device(sg_engine* e, uint64_t n) {
+    hipStream_t st = e->stream;
     const uint32_t nflows = (uint32_t)e->cflows.size();
-    // requests and results may be host or device memory (dist.request_tokens keeps them in HBM under RCCL)
-    HIPCHK(hipMemcpyAsync(e->d_treq, reqs, n * sizeof(sg_token_req), hipMemcpyDefault, st));
     HIPCHK(hipMemsetAsync(e->d_small, 0, 4, st));
     const uint32_t nns = (uint32_t)e->ns_names.size();
     const bool grouped = nns > 1 || e->tok_ns;  // several limiters: the namespace-grouped limiter step
@@ -4270,7 +4416,7 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
     if (flags & 1) return fail(SG_EINVAL, "token requests must be ordered by ts (the replay clock)");
     // GlobalRequestLimiter: a negative qpsAllowed stands for "no limiter registered" (tryPass -> true)
     const double allowed = e->ns_limit[0] < 0 ? 1.0 / 0.0 : e->ns_limit[0];
-    // the limiter (parallel per 100 ms bucket; the drained batch slot's arrays are its scratch), then the flows
+    // the limiter (parallel per 100 ms bucket; the batch slot's arrays are its scratch), then the flows
     uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
     if (grouped) {
         if (int rc2 = tok_limiter_grouped(e, n, nflows, kin, vin, kout, vout)) return rc2;
@@ -4295,14 +4441,127 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
             e->tbounds_cap = std::max<uint32_t>(nflows + 1, 1u << 12);
             HIPCHK(hipMalloc(&e->d_tbounds, (uint64_t)e->tbounds_cap * 4));
         }
-        // (the decide streams are idle: every batch was drained above)
+        // (the other decide streams are idle: every earlier batch is decided, see above)
         HIPCHK(launch_tok_flow(kin, vin, n, e->d_treq, e->d_cflow, nflows, e->d_cbkt, e->cfg.cluster_exceed_count,
                                e->cfg.cluster_max_occupy_ratio, e->d_tres, e->d_tbounds, e->tok_light, e->tok_wide, st,
                                e->bin_stream[0], e->fork, e->join[0]));
     }
+    return SG_OK;
+}
+int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n, sg_token_result* out) {
+    if (!e || (n && (!reqs || !out))) return fail(SG_EINVAL, "null argument");
+    if (!n) return SG_OK;
+    if (n > 0x7FFFFFFFull) return fail(SG_EINVAL, "too many token requests in one call");
+    if (int rc = drain(e)) return rc;
+    hipStream_t st = e->stream;
+    if (int rc = tok_ensure(e, n)) return rc;
+    // requests and results may be host or device memory (dist.request_tokens keeps them in HBM under RCCL)
+    HIPCHK(hipMemcpyAsync(e->d_treq, reqs, n * sizeof(sg_token_req), hipMemcpyDefault, st));
+    if (int rc = tok_device(e, n)) return rc;
     HIPCHK(hipMemcpyAsync(out, e->d_tres, n * sizeof(sg_token_result), hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));
     return SG_OK;
+}
+
+// Embedded token server, the decide stage's step for batch slot k (decide_enqueue, after the chain grants): the
+// ENTRYs that ask for a token are compacted in submission order into e->d_treq (kernels.hip k_emb_count /
+// k_emb_scatter, the test in embedded.h), one token call decides them, and k_emb_answers leaves each answer's side
+// word at the ENTRY's sorted position (e->d_emb_side, cleared first) and counts the answers (d_bsmall[101..107]; [100]
+// the requests).  The token call's scratch is the other slot's arrays: its batch is decided (submit_impl hands a batch
+// with XF_EMB events off before the next group stage is enqueued), and the call runs on the engine stream behind it.
+// The host waits twice (the request count, the classification's flag): such a batch overlaps with no neighbour.
+static int embedded_tokens(sg_engine* e, int k, uint32_t* nreq_out) {
+    auto& B = e->slot[k];
+    const auto& G = B.g;
+    hipStream_t st = e->stream;
+    const uint64_t n = G.n;
+    if (e->cap_n > e->emb_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        dfree(e->d_emb_side); dfree(e->d_emb_idx); dfree(e->d_emb_cnt); dfree(e->d_emb_part);
+        const uint64_t c = e->cap_n, nt = c / 1024 + 2;
+        HIPCHK(hipMalloc(&e->d_emb_side, c * 4));
+        HIPCHK(hipMalloc(&e->d_emb_idx, c * 4));
+        HIPCHK(hipMalloc(&e->d_emb_cnt, nt * 4));
+        HIPCHK(hipMalloc(&e->d_emb_part, (nt / 4096 + 2) * 4));
+        e->emb_cap = c;
+    }
+    uint32_t* bs = B.d_bsmall;
+    for (auto& x : e->emb_t)
+        if (!x) HIPCHK(hipEventCreate(&x));
+    e->emb_timed = false;
+    HIPCHK(hipEventRecord(e->emb_t[0], st));
+    HIPCHK(launch_emb_count(G.dev_ev, G.dev_ext, n, e->cfg.max_resources, SG_MAX_CONTEXTS, e->d_prog, e->d_info, dev_auth(e),
+                            dev_auth_ids(e), e->cfg.switch_on, e->d_emb_cnt, e->d_emb_part, bs + 100, st));
+    uint32_t nreq = 0;
+    HIPCHK(hipMemcpyAsync(&nreq, bs + 100, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *nreq_out = nreq;
+    if (!nreq) return SG_OK;
+    if (int rc = tok_ensure(e, nreq)) return rc;  // (nreq <= n <= cap_n: the batch arrays stay)
+    HIPCHK(launch_emb_scatter(G.dev_ev, G.dev_ext, n, e->cfg.max_resources, SG_MAX_CONTEXTS, e->d_prog, e->d_info,
+                              dev_auth(e), dev_auth_ids(e), e->cfg.switch_on, e->d_emb_cnt, e->d_emb_flow, nreq, e->d_treq,
+                              e->d_emb_idx, st));
+    HIPCHK(hipEventRecord(e->emb_t[1], st));
+    activate(e, k ^ 1);
+    const int rc = tok_device(e, nreq);
+    activate(e, k);
+    if (rc) return rc;
+    // the call's last kernels are still in flight: the next group stage into the borrowed slot waits for them
+    if (!e->emb_ev[k ^ 1]) HIPCHK(hipEventCreateWithFlags(&e->emb_ev[k ^ 1], hipEventDisableTiming));
+    HIPCHK(hipEventRecord(e->emb_ev[k ^ 1], st));
+    e->slot[k ^ 1].lent = e->emb_ev[k ^ 1];
+    HIPCHK(hipEventRecord(e->emb_t[2], st));
+    HIPCHK(hipMemsetAsync(e->d_emb_side, 0, n * 4, st));
+    HIPCHK(launch_emb_answers(e->d_tres, e->d_emb_idx, nreq, B.radix ? B.d_posof : nullptr, B.d_flag, B.d_pos, B.nhot, n,
+                              e->d_emb_side, bs + 101, st));
+    HIPCHK(hipEventRecord(e->emb_t[3], st));
+    e->emb_timed = true;
+    return SG_OK;
+}
+
+// diagnostics export, for synchronous batches only (one set of events an engine: with a second embedded batch decided
+// before the first is collected the values are stale or 0): device times of the embedded steps in the last collected
+// batch that made requests, ms: [0] the
+// extraction (both kernels, the scan and the host's wait for the count between them), [1] the token call, [2] the
+// side array's clear and the answers' scatter.  Returns the values written.
+extern "C" int sgx_embedded_ms(sg_engine* e, double* out, int cap) {
+    if (!e || !out) return 0;
+    drain_hold(e);
+    int k = 0;
+    for (; k < 3 && k < cap; ++k) out[k] = e->emb_ms[k];
+    return k;
+}
+
+// ClusterStateManager's server state (embedded mode, embedded.h): on, the flow rules' cluster rules are decided on the
+// decision path by this engine's own token server; off (the default), as in a process without a TokenService.  The
+// programs are compiled again; node, breaker and token state stay.  Switching on over a cluster rule outside the
+// supported shape is refused (SG_ENOTSUP, sg_last_error names the rule) and changes nothing.
+int sg_cluster_embedded(sg_engine* e, int32_t on) {
+    if (!e) return fail(SG_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = drain(e)) return rc;
+    const bool want = on != 0;
+    if (want == e->emb_on) return SG_OK;
+    if (want)
+        if (int rc = emb_refuse(e, e->flows, e->res_flow, e->res_par)) return rc;
+    e->emb_on = want;
+    const int rc = upload_rules(e, false, false, false);
+    if (rc) {
+        e->emb_on = !want;
+        return rc;
+    }
+    return SG_OK;
+}
+// diagnostics export: the embedded token server's part of the last collected batch: [0] requests issued, [1..7]
+// answers OK, BLOCKED, SHOULD_WAIT, TOO_MANY_REQUEST, BAD_REQUEST, FAIL, NO_RULE_EXISTS, [8] words written ahead of the
+// cooperative owners, [9] segments of embedded resources in cooperative bins, [10] in lane bins, [11] in the late
+// lane pass (always 0: no fallback rules).  Returns the values written.
+extern "C" int sgx_embedded_last(sg_engine* e, unsigned long long* out, int cap) {
+    if (!e || !out) return 0;
+    drain_hold(e);
+    int k = 0;
+    for (; k < EMB_LAST_WORDS && k < cap; ++k) out[k] = e->emb_last[k];
+    return k;
 }
 
 // Room in the value table for a call of V listed values, before any kernel of the call runs (pvtab.h; in the

@@ -14,6 +14,7 @@
 #include "../../include/sentinel_gpu.h"
 #include "authority.h"
 #include "dev_types.h"
+#include "embedded.h"
 
 using namespace sg;
 
@@ -1440,6 +1441,137 @@ hipError_t launch_snapshot(Bkt* minb, NodeInfo* info, uint32_t nres, int64_t now
     hipError_t e = launch_scan(cnt, off, nres, part, total, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_snap_emit, dim3(nb), dim3(256), 0, st, minb, info, nres, now, off, outp, cap);
+    return hipGetLastError();
+}
+
+// =================================================================================
+// embedded token server (embedded.h): the batch's token requests and their answers
+// =================================================================================
+// The ENTRYs of the batch that ask for a cluster token (embedded.h emb_requests), compacted in submission order --
+// which is time order, the order DefaultTokenService sees them in -- into sg_token_req records: per-tile counts
+// (k_emb_count), an exclusive scan, and the scatter (k_emb_scatter), which evaluates the same test again.  Both run
+// after the batch's chain grants (the test reads NI_CHAIN).  A lane holds EMB_ITEMS consecutive events, so a
+// tile's requests are ordered by (lane, item) and one block scan places them.  idx[j]: the batch index of request j.
+#define EMB_THREADS 256
+#define EMB_ITEMS 4
+#define EMB_TILE (EMB_THREADS * EMB_ITEMS)
+static_assert(EMB_THREADS == SC_THREADS, "block_excl_scan is sized for SC_THREADS lanes");
+struct EmbIn {
+    const sg_event* ev;
+    const sg_event_ext* ext;   // null: sg_submit (no origin, the default context)
+    uint64_t n;
+    uint32_t max_res, max_ctx;
+    const Prog* prog;
+    const NodeInfo* info;
+    const AuthDesc* auth;      // null unless authority rules are loaded
+    const uint32_t* auth_ids;
+    int32_t switch_on;
+};
+__device__ __forceinline__ bool emb_event_requests(const EmbIn& I, uint64_t i, sg_event& e) {
+    if (i >= I.n) return false;
+    e = I.ev[i];
+    if (e.kind != SG_EV_ENTRY || e.res_id >= I.max_res) return false;
+    const uint32_t xf = I.prog[e.res_id].xf;
+    if (!(xf & XF_EMB)) return false;  // (the common case: nothing more is read)
+    uint32_t origin = 0, ctx = 0;
+    if (I.ext) {
+        const sg_event_ext x = I.ext[i];
+        origin = x.origin_id;
+        ctx = x.context_id;
+    }
+    const bool ab = I.auth != nullptr && origin != 0 && auth_blocks(I.auth, I.auth_ids, e.res_id, origin);
+    return emb_requests(e.kind, e.flags, xf, I.info[e.res_id].flags, I.switch_on, ctx, I.max_ctx, ab);
+}
+__global__ __launch_bounds__(EMB_THREADS) void k_emb_count(EmbIn I, uint32_t* __restrict__ cnt) {
+    const uint64_t base = (uint64_t)blockIdx.x * EMB_TILE + (uint64_t)threadIdx.x * EMB_ITEMS;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < EMB_ITEMS; ++k) {
+        sg_event e;
+        c += emb_event_requests(I, base + k, e) ? 1u : 0u;
+    }
+    uint32_t tot;
+    (void)block_excl_scan(c, &tot);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(EMB_THREADS) void k_emb_scatter(EmbIn I, const uint32_t* __restrict__ off,
+                                                             const int64_t* __restrict__ flow_of, uint32_t cap,
+                                                             sg_token_req* __restrict__ req, uint32_t* __restrict__ idx) {
+    const uint64_t base = (uint64_t)blockIdx.x * EMB_TILE + (uint64_t)threadIdx.x * EMB_ITEMS;
+    sg_event e[EMB_ITEMS];
+    bool q[EMB_ITEMS];
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < EMB_ITEMS; ++k) {
+        q[k] = emb_event_requests(I, base + k, e[k]);
+        c += q[k] ? 1u : 0u;
+    }
+    uint32_t o = off[blockIdx.x] + block_excl_scan(c, nullptr);
+#pragma unroll
+    for (int k = 0; k < EMB_ITEMS; ++k) {
+        if (!q[k]) continue;
+        if (o < cap) {  // (cap = the count the host read after the scan: never exceeded)
+            sg_token_req r;
+            r.ts = e[k].ts;
+            r.flow_id = flow_of[e[k].res_id];
+            r.acquire_count = (int32_t)e[k].count;
+            r.prioritized = (e[k].flags & SG_F_PRIORITIZED) ? 1 : 0;
+            req[o] = r;
+            idx[o] = (uint32_t)(base + k);
+        }
+        ++o;
+    }
+}
+// Each answer to its ENTRY's sorted position: the side word the owners read (embedded.h emb_word; side[] was cleared
+// for the batch) and the answers by class (stat[EMB_A_*]).  The position comes from the group stage's inverse
+// permutation: pos_of (the radix stage) or the hot / cold stage's words and P, as k_post / k_post_w walk it back.
+__global__ __launch_bounds__(256) void k_emb_answers(const sg_token_result* __restrict__ res,
+                                                     const uint32_t* __restrict__ idx, uint32_t nreq,
+                                                     const uint32_t* __restrict__ pos_of,
+                                                     const uint32_t* __restrict__ words, const uint32_t* __restrict__ P,
+                                                     uint32_t nhot, uint64_t n, uint32_t* __restrict__ side,
+                                                     uint32_t* __restrict__ stat) {
+    __shared__ uint32_t sc[EMB_A_N];
+    if (threadIdx.x < EMB_A_N) sc[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j < nreq) {
+        const uint32_t i = idx[j];
+        const sg_token_result a = res[j];
+        atomicAdd(&sc[emb_answer_class(a.status)], 1u);
+        // (an eligible resource's cluster rule is its only flow rule: slot 0 of its compiled list)
+        const uint32_t w = emb_word(a.status, a.wait_in_ms, 0u);
+        if (w && i < n) {
+            const uint32_t p = pos_of ? (pos_of[i] & 0x7FFFFFFFu) : grp_pos(i, words[i], P, nhot);
+            if (p < n) side[p] = w;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < EMB_A_N && sc[threadIdx.x]) atomicAdd(&stat[threadIdx.x], sc[threadIdx.x]);
+}
+hipError_t launch_emb_count(const sg_event* ev, const sg_event_ext* ext, uint64_t n, uint32_t max_res, uint32_t max_ctx,
+                            const Prog* prog, const NodeInfo* info, const AuthDesc* auth, const uint32_t* auth_ids,
+                            int32_t switch_on, uint32_t* cnt, uint32_t* part, uint32_t* total, hipStream_t st) {
+    const EmbIn I{ev, ext, n, max_res, max_ctx, prog, info, auth, auth_ids, switch_on};
+    const uint32_t nt = (uint32_t)((n + EMB_TILE - 1) / EMB_TILE);
+    hipLaunchKernelGGL(k_emb_count, dim3(nt), dim3(EMB_THREADS), 0, st, I, cnt);
+    return launch_scan(cnt, cnt, nt, part, total, st);
+}
+hipError_t launch_emb_scatter(const sg_event* ev, const sg_event_ext* ext, uint64_t n, uint32_t max_res, uint32_t max_ctx,
+                              const Prog* prog, const NodeInfo* info, const AuthDesc* auth, const uint32_t* auth_ids,
+                              int32_t switch_on, const uint32_t* off, const int64_t* flow_of, uint32_t cap,
+                              sg_token_req* req, uint32_t* idx, hipStream_t st) {
+    const EmbIn I{ev, ext, n, max_res, max_ctx, prog, info, auth, auth_ids, switch_on};
+    const uint32_t nt = (uint32_t)((n + EMB_TILE - 1) / EMB_TILE);
+    hipLaunchKernelGGL(k_emb_scatter, dim3(nt), dim3(EMB_THREADS), 0, st, I, off, flow_of, cap, req, idx);
+    return hipGetLastError();
+}
+hipError_t launch_emb_answers(const sg_token_result* res, const uint32_t* idx, uint32_t nreq, const uint32_t* pos_of,
+                              const uint32_t* words, const uint32_t* P, uint32_t nhot, uint64_t n, uint32_t* side,
+                              uint32_t* stat, hipStream_t st) {
+    if (!nreq) return hipSuccess;
+    hipLaunchKernelGGL(k_emb_answers, dim3((nreq + 255) / 256), dim3(256), 0, st, res, idx, nreq, pos_of, words, P, nhot, n,
+                       side, stat);
     return hipGetLastError();
 }
 

@@ -29,7 +29,7 @@ EXPORTS = (
     "sg_cluster_namespace_qps", "sg_load_authority_rules", "sg_param_intern", "sg_param_intern_batch",
     "sg_param_keys_sweep", "sg_param_keys_stats", "sg_cluster_param_table_stats",
     "sg_track_inbound", "sg_read_inbound_node", "sg_inbound_metrics",
-    "sg_cluster_metrics", "sg_param_key_value",
+    "sg_cluster_metrics", "sg_param_key_value", "sg_cluster_embedded",
 )
 
 
@@ -112,6 +112,14 @@ def _cmetrics(name):
     fn = getattr(lib(), name)
     if fn.argtypes is None:
         fn.argtypes = _CMETRICS_ARGS[name]()
+    return fn
+
+
+# the embedded token server's entry point, bound on first use for the same reason
+def _embedded():
+    fn = lib().sg_cluster_embedded
+    if fn.argtypes is None:
+        fn.argtypes = [C.c_void_p, C.c_int32]
     return fn
 
 
@@ -459,6 +467,43 @@ class Engine:
         return n.value
 
     # ---- token server (sg_cluster_*; DefaultTokenService.requestToken, csrv/flow/DefaultTokenService.java:37-48)
+    # ---- embedded token server: ClusterStateManager's server state (sg_cluster_embedded)
+    EMBEDDED_STATS = ("requests", "ok", "blocked", "should_wait", "too_many_request", "bad_request", "fail",
+                      "no_rule_exists", "words_ahead", "coop_segments", "lane_segments", "late_segments")
+
+    def cluster_embedded(self, on: bool = True):
+        """Decide the flow rules' cluster rules on the decision path with this engine's own token server (embedded
+        mode).  Off by default: a cluster rule is then decided as without a TokenService.  SentinelError SG_ENOTSUP,
+        with nothing changed, if a loaded cluster flow rule lies outside the supported shape (sentinel_gpu.h)."""
+        _check(_embedded()(self.h, 1 if on else 0))
+
+    def cluster_embedded_stats(self) -> dict:
+        """The embedded token server's part of the last collected batch: token requests issued, answers by status,
+        BLOCKED words written ahead of the cooperative owners, segments of embedded resources in cooperative bins, in
+        lane bins and in the late lane pass (always 0: fallback rules are not taken).  Diagnostics export
+        sgx_embedded_last; drains the pipeline first."""
+        fn = lib().sgx_embedded_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        k = len(self.EMBEDDED_STATS)
+        out = np.zeros(k, dtype=np.uint64)
+        if fn(self.h, out.ctypes.data, k) != k:
+            raise SentinelError(A.SG_EDEVICE, "sgx_embedded_last failed")
+        return {name: int(v) for name, v in zip(self.EMBEDDED_STATS, out)}
+
+    def cluster_embedded_ms(self):
+        """Device times [ms] of the embedded steps in the last collected batch that made requests: the extraction
+        (with the host's wait for the request count), the token call, the answers' scatter (diagnostics export
+        sgx_embedded_ms; drains the pipeline first).  For synchronous batches only: the engine keeps one set of timing
+        events, so with a second embedded batch decided before the first is collected the values are stale or 0."""
+        fn = lib().sgx_embedded_ms
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        out = np.zeros(3, dtype=np.float64)
+        if fn(self.h, out.ctypes.data, 3) != 3:
+            raise SentinelError(A.SG_EDEVICE, "sgx_embedded_ms failed")
+        return {"extract": float(out[0]), "token_call": float(out[1]), "scatter": float(out[2])}
+
     def cluster_set_connected(self, flow_id: int, n: int):
         _check(lib().sg_cluster_set_connected_count(self.h, int(flow_id), int(n)))
 
