@@ -29,6 +29,7 @@
 
 #include "chain.h"
 #include "cmwin.h"
+#include "launch.h"
 #include "ptok.h"
 #include "pvtab.h"
 
@@ -664,15 +665,13 @@ hipError_t launch_tok_limiter_ns(const sg_token_req* req, uint64_t n, const uint
                                  const uint32_t* fidx, uint32_t nflows, NsLimiter* lims, const double* limits,
                                  uint32_t nns, uint32_t* keys, uint32_t* vals, sg_token_result* res, uint32_t* bflag,
                                  uint32_t* bidx, uint32_t* bstart, uint32_t* kpass, uint32_t* part, uint32_t* small,
-                                 uint32_t* nsb,
-                                 hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                                 hipStream_t st) {
+                                 uint32_t* nsb, hipStream_t st) {
     if (!n) return hipSuccess;
     const uint32_t g = (uint32_t)((n + 255) / 256);
     hipError_t e = hipMemsetAsync(nsb, 0, (size_t)nns * 8, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_nsl_flags, dim3(g), dim3(256), 0, st, req, n, sk, sv, nns, bflag, small);
-    if ((e = scan(bflag, bidx, n, part, small, st)) != hipSuccess) return e;
+    if ((e = launch_scan(bflag, bidx, n, part, small, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_nsl_starts, dim3(g), dim3(256), 0, st, sk, n, nns, bflag, bidx, bstart, nsb);
     hipLaunchKernelGGL(k_nsl_walk, dim3(nns), dim3(64), 0, st, req, sv, bstart, nsb, small, lims, limits, nns, kpass);
     hipLaunchKernelGGL(k_nsl_apply, dim3(g), dim3(256), 0, st, n, sk, sv, nns, fidx, bflag, bidx, bstart, kpass, nflows,
@@ -714,14 +713,12 @@ hipError_t launch_tok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_
 hipError_t launch_tok_limiter_par(const sg_token_req* req, uint64_t n, const uint32_t* fidx, uint32_t nflows,
                                   NsLimiter* lim, double allowed, uint32_t* keys, uint32_t* vals, sg_token_result* res,
                                   uint32_t* bflag, uint32_t* cflag, uint32_t* bidx, uint32_t* cexcl, uint32_t* bstart,
-                                  uint32_t* kpass, uint32_t* part, uint32_t* small,
-                                  hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                                  hipStream_t st) {
+                                  uint32_t* kpass, uint32_t* part, uint32_t* small, hipStream_t st) {
     if (!n) return hipSuccess;
     const uint32_t g = (uint32_t)((n + 255) / 256);
     hipLaunchKernelGGL(k_lim_flags, dim3(g), dim3(256), 0, st, req, n, fidx, bflag, cflag);
-    hipError_t e = scan(bflag, bidx, n, part, small, st);
-    if (e == hipSuccess) e = scan(cflag, cexcl, n, part, small + 1, st);
+    hipError_t e = launch_scan(bflag, bidx, n, part, small, st);
+    if (e == hipSuccess) e = launch_scan(cflag, cexcl, n, part, small + 1, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_lim_starts, dim3(g), dim3(256), 0, st, bidx, bflag, n, bstart);
     hipLaunchKernelGGL(k_lim_walk, dim3(1), dim3(64), 0, st, req, n, bstart, small, cexcl, small + 1, lim, allowed, kpass);
@@ -1060,12 +1057,7 @@ hipError_t launch_ptok_vp(const uint32_t* skeys, const uint32_t* svals, uint64_t
                           uint32_t mask, const uint32_t* serial, uint32_t* dedup, uint32_t dmask, uint32_t* slotof,
                           uint32_t* rep, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, int64_t* dts,
                           int32_t* dacq, uint32_t* hist, uint32_t* part, uint32_t tile, sg_token_result* res,
-                          uint32_t* flags, unsigned long long* ctr,
-                          hipError_t (*rhist)(const uint32_t*, uint64_t, int, uint32_t*, uint32_t, hipStream_t),
-                          hipError_t (*rscatter)(const uint32_t*, const uint32_t*, uint64_t, int, const uint32_t*, uint32_t,
-                                                 uint32_t*, uint32_t*, uint32_t*, hipStream_t),
-                          hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                          hipStream_t st) {
+                          uint32_t* flags, unsigned long long* ctr, hipStream_t st) {
     if (!n || !nflows) return hipSuccess;
     const uint32_t g = (uint32_t)((n + 255) / 256);
     hipError_t e = hipMemsetAsync(dedup, 0xFF, ((size_t)dmask + 1) * 4, st);
@@ -1082,9 +1074,9 @@ hipError_t launch_ptok_vp(const uint32_t* skeys, const uint32_t* svals, uint64_t
     const int passes = (bits + 7) / 8;
     const uint32_t nblocks = (uint32_t)((n + tile - 1) / tile);
     for (int p = 0; p < passes; ++p) {
-        if ((e = rhist(ka, n, p * 8, hist, nblocks, st)) != hipSuccess) return e;
-        if ((e = scan(hist, hist, (uint64_t)nblocks * 256, part, nullptr, st)) != hipSuccess) return e;
-        if ((e = rscatter(ka, va, n, p * 8, hist, nblocks, kb, vb, nullptr, st)) != hipSuccess) return e;
+        if ((e = launch_radix_hist(ka, n, p * 8, hist, nblocks, st)) != hipSuccess) return e;
+        if ((e = launch_scan(hist, hist, (uint64_t)nblocks * 256, part, nullptr, st)) != hipSuccess) return e;
+        if ((e = launch_radix_scatter(ka, va, n, p * 8, hist, nblocks, kb, vb, nullptr, st)) != hipSuccess) return e;
         uint32_t* t = ka; ka = kb; kb = t;
         t = va; va = vb; vb = t;
     }

@@ -29,6 +29,7 @@
 #include "../../include/sentinel_gpu.h"
 #include "cmwin.h"
 #include "dev_types.h"
+#include "launch.h"
 
 namespace sg {
 
@@ -318,12 +319,11 @@ hipError_t launch_cm_scan(const PVal* tab, uint64_t n_slots, const PFlow* flows,
 hipError_t launch_cm_select(const uint32_t* skeys, const uint32_t* svals, uint32_t n, const PFlow* flows, uint32_t nflows,
                             const int64_t* csum, const uint64_t* ckey, uint32_t top_n, uint32_t* bounds, uint32_t* nch,
                             uint32_t* coff, uint32_t* part, int64_t* psum, uint64_t* pkey, sg_cluster_metric* prows,
-                            hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
                             hipEvent_t* ev, hipStream_t st) {
     if (!n || !nflows) return hipSuccess;
     hipLaunchKernelGGL(k_cm_bounds, dim3((n + 256) / 256), dim3(256), 0, st, skeys, n, nflows, bounds);
     hipLaunchKernelGGL(k_cm_chunks, dim3((nflows + 256) / 256), dim3(256), 0, st, bounds, nflows, nch);
-    hipError_t rc = scan(nch, coff, (uint64_t)nflows + 1, part, nullptr, st);
+    hipError_t rc = launch_scan(nch, coff, (uint64_t)nflows + 1, part, nullptr, st);
     if (rc == hipSuccess) rc = hipEventRecord(ev[0], st);
     if (rc != hipSuccess) return rc;
     const uint32_t max_chunks = n / CM_CHUNK + nflows;  // sum of ceil(len / CM_CHUNK) over the non-empty flows, at most

@@ -29,6 +29,7 @@
 
 #include "authority.h"
 #include "embedded.h"
+#include "launch.h"
 #include "chain.h"
 #include "aux.h"
 #include "pmap.h"
@@ -4188,12 +4189,11 @@ __global__ __launch_bounds__(TINY_MAX) void k_tiny(const sg_event* __restrict__ 
 namespace sg {
 
 hipError_t launch_seg(const uint32_t* keys, uint64_t n, uint32_t* flag, uint32_t* pos, Seg* segs, hipStream_t st,
-                      hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
                       uint32_t* part, uint32_t* nseg) {
     // flag/pos are scratch of >= n words: tile counts in flag, their offsets in pos
     const uint32_t nt = (uint32_t)((n + SEG_TILE - 1) / SEG_TILE);
     hipLaunchKernelGGL(k_seg_count, dim3(nt), dim3(256), 0, st, keys, n, flag, (const uint32_t*)nullptr);
-    hipError_t e = scan(flag, pos, nt, part, nseg, st);
+    hipError_t e = launch_scan(flag, pos, nt, part, nseg, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_seg_emit, dim3(nt), dim3(256), 0, st, keys, n, pos, segs, (const uint32_t*)nullptr,
                        (const uint32_t*)nullptr);
@@ -4205,12 +4205,10 @@ __global__ void k_add2(uint32_t* __restrict__ dst, const uint32_t* __restrict__ 
 // the cold segments of the hot / cold group stage: keys[*lo, n), written after the *sbase hot ones; nseg = both.
 // flag / pos: scratch of >= n / SEG_TILE + 1 words each; ccount: one device word
 hipError_t launch_seg_cold(const uint32_t* keys, uint64_t n, const uint32_t* lo, const uint32_t* sbase, uint32_t* flag,
-                           uint32_t* pos, Seg* segs, hipStream_t st,
-                           hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                           uint32_t* part, uint32_t* ccount, uint32_t* nseg) {
+                           uint32_t* pos, Seg* segs, hipStream_t st, uint32_t* part, uint32_t* ccount, uint32_t* nseg) {
     const uint32_t nt = (uint32_t)((n + SEG_TILE - 1) / SEG_TILE);
     hipLaunchKernelGGL(k_seg_count, dim3(nt), dim3(256), 0, st, keys, n, flag, lo);
-    hipError_t e = scan(flag, pos, nt, part, ccount, st);
+    hipError_t e = launch_scan(flag, pos, nt, part, ccount, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_seg_emit, dim3(nt), dim3(256), 0, st, keys, n, pos, segs, lo, sbase);
     hipLaunchKernelGGL(k_add2, dim3(1), dim3(64), 0, st, nseg, sbase, ccount);
@@ -4303,8 +4301,6 @@ hipError_t launch_tiny(const sg_event* ev, uint32_t n, const DevState& S, const 
     return hipGetLastError();
 }
 uint32_t tiny_max() { return TINY_MAX; }
-hipError_t launch_head(const SEv* recs, const Seg* segs, const uint32_t* order, uint32_t m, const DevState& S,
-                       const DevCfg& cfg, int64_t t0, uint32_t* dec, uint32_t* bflags, hipStream_t st);
 hipError_t launch_decide_bin(int bin, const SEv* recs, const sg_event* ev, const uint32_t* vals, const Seg* segs,
                              const uint32_t* order, uint32_t m, const DevState& S, const DevCfg& cfg, int64_t t0,
                              uint32_t* dec, uint32_t* bflags, hipStream_t st) {

@@ -565,4 +565,64 @@ enum : uint32_t {
     N_BINS = BIN_LITE + LANE_BINS       // <= 63: k_bin_offsets runs one 64-lane wave
 };
 
+// The words of a batch slot's small block (BatchSlot::d_bsmall, BS_WORDS of them), which the host and the kernels
+// share: k_grp_clear zeroes the block at the start of the slot's group stage, the kernels get the address of the
+// word they write, and the host reads two prefixes of it from pinned copies -- BS_HEAD_WORDS after the group stage
+// (accept_grouped, decide_enqueue), BS_MIRROR_WORDS after the decide stage (collect).
+enum : uint32_t {
+    BS_FLAGS = 0,        // BF_* of the batch: the group stage's checks, then what the decide kernels raise
+    BS_NSEG = 1,         // segments
+    BS_NCAND = 2,        // chain candidates (k_chain, under a finite chain cap)
+    BS_NPREV = 3,        // references into earlier batches (k_resolve's list)
+    BS_T0 = 4,           // [4..5] int64: ts of the batch's first event
+    BS_MIX_N = 6,        // XF_MIX segments of the cooperative bins: narrow, [7] wide
+    BS_MIX_NW = 7,
+    BS_BIN_OFF = 8,      // [8 .. 8 + N_BINS]: the bins' offsets in order[]
+    BS_MIX_WIDE = 72,    // events of the wide XF_MIX segments
+    BS_HOT_MARKED = 73,  // hot ids k_seg_bin marked for the side tables
+    BS_UBLK = 74,        // PM_UBLK segments in cooperative bins (SEG_UBLK), [75] in lane bins
+    BS_UBLK_LANE = 75,
+    BS_HOT_NEXT = 76,    // the next batch's hot ids
+    BS_GRP = 77,         // the hot / cold group stage's own: hot_total (the cold region's start), [78] cold events
+    BS_COLD_N = 78,
+    BS_HOT_SEGS = 80,    // hot segments, [81] hot_total again, [82] cold segments
+    BS_COLD_SEGS = 82,
+    BS_EMB = 83,         // events of XF_EMB segments, [84] XF_EMB segments in cooperative bins, [85] in lane bins
+    BS_EMB_COOP = 84,
+    BS_EMB_LANE = 85,
+    BS_HEAD_WORDS = BS_EMB_LANE + 1,    // 86: the last word the host reads after the group stage + 1
+    BS_EMB_REQ = 100,    // embedded token server: the batch's requests, [101..107] its answers by class (EMB_A_*)
+    BS_EMB_ANS = 101,
+    BS_EMB_AHEAD = 108,  // ... and the words written ahead of the cooperative owners
+    BS_UBLK_WORDS = 119, // RF_UBLK words written (k_ublk_words)
+    BS_NSPAN = 120,      // frozen spans recorded (DevState.nspan)
+    BS_MIRROR_WORDS = BS_NSPAN + 1,     // 121: the last word collect() reads + 1
+    BS_AUX = 130,        // [130..133] counts of the aux.hip post-pass lists k_seg_bin builds
+    BS_AUX_POOL_N = 134, // partials taken from the aux pool
+    BS_WORDS = 256
+};
+static_assert(BS_BIN_OFF + N_BINS + 1 <= BS_MIX_WIDE, "the bin offsets end below the next word");
+// The head copy: accept_grouped() reads BS_FLAGS, BS_MIX_NW, BS_MIX_WIDE, BS_HOT_MARKED, BS_UBLK, BS_UBLK_LANE,
+// BS_HOT_NEXT and BS_EMB .. BS_EMB_LANE (the highest: BS_HEAD_WORDS is that word + 1); decide_enqueue() reads BS_FLAGS,
+// BS_NSEG, BS_NPREV, both words of BS_T0, BS_MIX_N, BS_MIX_NW, the N_BINS + 1 bin offsets, BS_MIX_WIDE and BS_UBLK.
+static_assert(BS_T0 + 1 < BS_MIX_N && BS_MIX_NW < BS_BIN_OFF && BS_BIN_OFF + N_BINS < BS_HEAD_WORDS &&
+                  BS_MIX_WIDE < BS_HEAD_WORDS && BS_HOT_MARKED < BS_HEAD_WORDS && BS_UBLK_LANE < BS_HEAD_WORDS &&
+                  BS_HOT_NEXT < BS_HEAD_WORDS && BS_EMB + 2 == BS_EMB_LANE && BS_HEAD_WORDS == BS_EMB_LANE + 1,
+              "accept_grouped() and decide_enqueue() read the head copy only");
+// The mirror copy: collect() reads BS_FLAGS, the nine words BS_EMB_REQ .. BS_EMB_AHEAD, BS_UBLK_WORDS and BS_NSPAN
+// (the highest: BS_MIRROR_WORDS is that word + 1).
+static_assert(BS_EMB_REQ + 1 == BS_EMB_ANS && BS_EMB_REQ + 8 == BS_EMB_AHEAD && BS_EMB_AHEAD < BS_UBLK_WORDS &&
+                  BS_UBLK_WORDS < BS_NSPAN && BS_MIRROR_WORDS == BS_NSPAN + 1 && BS_HEAD_WORDS <= BS_MIRROR_WORDS,
+              "collect() reads the mirror copy only");
+static_assert(BS_AUX_POOL_N < BS_WORDS, "small block size");
+
+// The engine-wide small block (sg_engine::d_small, SM_WORDS of them): scratch words of the calls that run on the
+// engine stream outside a batch.
+enum : uint32_t {
+    SM_FLAGS = 0,        // a call's flag word (token calls: 1 unordered requests, 2 value table full; k_pm_grow_ids: BF_*)
+    SM_SNAP_TOTAL = 3,   // sg_snapshot_metrics: rows
+    SM_LIMITER = 8,      // the parallel token limiters' words (cluster.hip launch_tok_limiter_par / _ns)
+    SM_WORDS = 256
+};
+
 } // namespace sg

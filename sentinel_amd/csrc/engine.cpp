@@ -25,233 +25,10 @@
 #include "authority.h"
 #include "dev_types.h"
 #include "embedded.h"
+#include "launch.h"
 #include "pkeys.h"
 #include "pmap.h"  // (pm_buckets: sg_param_thread_count)
 #include "pvtab.h"
-
-namespace sg {
-// kernels.hip
-hipError_t launch_rs_first(const sg_event* ev, uint64_t n, uint32_t max_res, uint64_t gbase, const uint8_t* ring,
-                           uint64_t ring_mask, int32_t max_rt, SEv* rec_o, uint32_t* keys, uint32_t* vals,
-                           uint32_t* ghist, uint32_t nblocks, uint32_t* bflags, int64_t* t0_out, uint32_t* prio,
-                           uint64_t* key_ring, const uint32_t* comp, const sg_event_ext* ext, const sg_arg* args,
-                           uint64_t n_args, uint32_t max_ctx, const AuthDesc* auth, const uint32_t* auth_ids,
-                           uint32_t ublk, hipStream_t st);
-// db = digit bits (8 or 10)
-hipError_t launch_radix_hist(const uint32_t* keys, uint64_t n, int shift, uint32_t* ghist, uint32_t nblocks,
-                             hipStream_t st);
-hipError_t launch_radix_hist_n(const uint32_t* keys, uint64_t n, const uint32_t* ndev, int shift, uint32_t* ghist,
-                               uint32_t nblocks, hipStream_t st);
-hipError_t launch_radix_scatter_n(const uint32_t* kin, const uint32_t* vin, uint64_t n, const uint32_t* ndev, int shift,
-                                  const uint32_t* goff, uint32_t nblocks, uint32_t* kout, uint32_t* vout, hipStream_t st);
-hipError_t launch_radix_scatter_x(const uint32_t* kin, const uint32_t* vin, uint64_t n, const uint32_t* ndev,
-                                  const uint32_t* tcnt, const uint32_t* dbase, int shift, const uint32_t* goff,
-                                  uint32_t nblocks, uint32_t* kout, uint32_t* vout, uint32_t* pos_of, hipStream_t st);
-hipError_t launch_grp_first(const sg_event* ev, uint64_t n, uint32_t max_res, uint64_t gbase, uint64_t ring_mask,
-                            uint32_t* bflags, int64_t* t0_out, uint32_t* prio, uint64_t* key_ring, const uint32_t* comp,
-                            const sg_event_ext* ext, const sg_arg* args, uint64_t n_args, uint32_t max_ctx,
-                            const AuthDesc* auth, const uint32_t* auth_ids,
-                            const uint16_t* hot_tab, uint32_t nhot, uint32_t nblocks, uint32_t* words,
-                            uint32_t* hot_hist, uint32_t* ckeys, uint32_t* cvals, uint32_t* ccnt, uint32_t* chist,
-                            uint32_t ublk, hipStream_t st);
-hipError_t launch_hot_scan(uint32_t* C, uint32_t nblocks, uint32_t nhot, uint32_t* part, uint32_t* hb, uint32_t* total,
-                           hipStream_t st);
-hipError_t launch_hot_bmax(const sg_event* ev, uint32_t nblocks, const uint32_t* P, uint32_t nhot, const uint32_t* hb,
-                           uint32_t* edges, uint32_t* bmax, hipStream_t st);
-hipError_t launch_grp_records(const sg_event* ev, uint64_t n, uint64_t gbase, uint64_t ring_mask, int32_t max_rt,
-                              const uint32_t* words, const uint32_t* P, uint32_t nhot, uint32_t nblocks,
-                              const uint32_t* hb, SEv* recs, uint32_t* svals, uint32_t* prev,
-                              uint32_t* nprev, uint32_t* bst, uint32_t* bflags, const sg_event_ext* ext,
-                              const sg_arg* args, uint32_t max_ctx, Link* link, uint32_t epoch,
-                              const uint32_t* need_hot, const uint32_t* need_blk, uint32_t max_res,
-                              const AuthDesc* auth, const uint32_t* auth_ids, uint32_t ublk, hipStream_t st);
-hipError_t launch_hot_segs(const uint32_t* hb, uint32_t nhot, const uint32_t* hot_list, Seg* segs, uint32_t* out,
-                           hipStream_t st);
-hipError_t launch_hot_build(const Seg* segs, const uint32_t* mp, uint32_t mb, uint32_t min_len, uint32_t max_res, uint16_t* hot_tab,
-                            uint32_t* hot_list, uint32_t nhot_old, uint32_t* hot_n, hipStream_t st);
-hipError_t launch_cold_n(uint64_t n, const uint32_t* hot_total, uint32_t* out, hipStream_t st);
-hipError_t launch_cold_small(const uint32_t* kin, const uint32_t* vin, const uint32_t* cnt, const uint32_t* dbase,
-                             uint32_t* kout, uint32_t* vout, uint32_t* words, hipStream_t st);
-uint32_t hot_max();
-hipError_t launch_grp_clear(uint32_t* bsmall, uint32_t nsmall, uint32_t* bst, uint32_t nbst, uint32_t* need,
-                            uint32_t nneed, hipStream_t st);
-hipError_t launch_seg_cold(const uint32_t* keys, uint64_t n, const uint32_t* lo, const uint32_t* sbase, uint32_t* flag,
-                           uint32_t* pos, Seg* segs, hipStream_t st,
-                           hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                           uint32_t* part, uint32_t* ccount, uint32_t* nseg);
-hipError_t launch_block_sums(const SEv* recs, uint64_t n, uint32_t* bst, Link* link, uint32_t epoch, uint32_t* bflags,
-                             const uint32_t* skeys, const uint32_t* lo, const uint32_t* need_blk, hipStream_t st);
-hipError_t launch_radix_scatter(const uint32_t* kin, const uint32_t* vin, uint64_t n, int shift, const uint32_t* goff,
-                                uint32_t nblocks, uint32_t* kout, uint32_t* vout, uint32_t* pos_of, hipStream_t st);
-uint32_t radix_tile();
-hipError_t launch_scan(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t);
-hipError_t launch_snapshot(Bkt*, NodeInfo*, uint32_t, int64_t, int32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*,
-                           sg_metric_node*, uint64_t, hipStream_t);
-hipError_t launch_init_state(Bkt* sec, Bkt* minb, NodeInfo* info, int64_t* borrow, uint32_t nres, hipStream_t st);
-hipError_t launch_set_flags(NodeInfo* info, const uint64_t* upd, uint32_t n, hipStream_t st);
-hipError_t launch_region_copy(const uint64_t* src, uint64_t* dst, const uint64_t* tri, uint32_t n, hipStream_t st);
-// decide.hip
-hipError_t launch_seg(const uint32_t* keys, uint64_t n, uint32_t* flag, uint32_t* pos, Seg* segs, hipStream_t st,
-                      hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                      uint32_t* part, uint32_t* nseg);
-hipError_t launch_seg_bin(Seg* segs, const uint32_t* mp, uint32_t mb, uint64_t n, const Prog* prog, const uint32_t* prio,
-                          uint32_t lane_max, uint32_t lite_max, uint32_t j1_max, uint32_t j4_max, uint32_t force_lane,
-                          uint32_t* blkcnt, uint32_t pq_ok, uint32_t pq_wide, uint32_t* aux, uint32_t* ashort, uint64_t* along,
-                          uint64_t* amulti, uint32_t* mixc, uint32_t* mix, uint32_t mix_cap, uint32_t* mixlen,
-                          uint32_t mix_wide, uint32_t head_min, const uint16_t* hot_tab, uint32_t nhot,
-                          const uint32_t* nhotseg, uint32_t* need_hot, uint32_t* need_blk, const uint32_t* bmax,
-                          uint32_t skip_min, uint32_t* nmark, uint32_t* ubc, uint32_t* embc, uint32_t max_res,
-                          hipStream_t st);
-// aux.hip
-hipError_t launch_aux(const SEv* recs, const Seg* segs, const uint32_t* aux, const uint32_t* ashort,
-                      const uint64_t* along, uint64_t* apiece, const uint64_t* amulti, const DevState& S, const DevCfg& cfg,
-                      int64_t t0, const uint32_t* dec, AuxAcc* pool, uint32_t pool_cap, uint32_t* pool_n, uint64_t* meta,
-                      uint32_t* bflags, hipStream_t st);
-hipError_t launch_aux_cold(const SEv* recs, const Seg* segs, const uint32_t* aux, const uint32_t* ashort, const DevState& S,
-                           const DevCfg& cfg, int64_t t0, const uint32_t* dec, uint32_t* bflags, hipStream_t st);
-// inbound.hip
-hipError_t launch_inbound(const SEv* recs, const uint32_t* dec, uint64_t n, const sg_event* ev, const uint32_t* vals,
-                          const DevState& S, const DevCfg& cfg, int64_t t0, InbPart* part, InbNode* node, hipStream_t st);
-// param.hip
-hipError_t launch_pq(int wide, const SEv* recs, const sg_event* ev, const uint32_t* vals, const Seg* segs,
-                     const uint32_t* order, uint32_t m, const DevState& S, const DevCfg& cfg, int64_t t0, uint32_t* dec,
-                     uint32_t* bflags, hipStream_t st);
-hipError_t launch_pm_grow(const Seg* segs, const uint32_t* mp, uint32_t mb, const DevState& S, unsigned long long* pool_next,
-                          uint64_t pool_nb, uint32_t* bflags, uint4* mv, uint32_t* nmv, uint32_t mcap, uint32_t epoch,
-                          uint32_t nm, PBucket* b2, PData* d2, uint32_t* sz, uint32_t* off, uint32_t* part,
-                          hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                          hipStream_t st);
-hipError_t launch_pm_compact(PMap* pm, uint32_t n, const PBucket* ob, const PData* od, PBucket* nbk, PData* nd,
-                             uint32_t* sz, uint32_t* off, uint32_t* part, unsigned long long* pool_next,
-                             hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                             hipStream_t st);
-hipError_t launch_pm_grow_ids(const uint32_t* ids, uint32_t n, const DevState& S, unsigned long long* pool_next,
-                              uint64_t pool_nb, uint32_t* bflags, hipStream_t st);
-hipError_t launch_pv_a(SEv* recs, const uint32_t* vals, Seg* segs, const uint32_t* list, uint32_t m,
-                       const DevState& S, const DevCfg& cfg, uint32_t* dec, PvSeg* pv, PvBuf B, uint32_t cap,
-                       uint32_t* tot, uint32_t* hist, uint32_t* part, hipStream_t st,
-                       hipError_t (*radix_hist)(const uint32_t*, uint64_t, const uint32_t*, int, uint32_t*, uint32_t, hipStream_t),
-                       hipError_t (*radix_scatter)(const uint32_t*, const uint32_t*, uint64_t, const uint32_t*, int,
-                                                   const uint32_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t),
-                       hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                       uint32_t tile, uint32_t* rest, uint32_t grant_all);
-hipError_t launch_pv_b(SEv* recs, Seg* segs, const uint32_t* list, uint32_t m, const DevState& S, int64_t t0,
-                       uint32_t* dec, uint32_t* bflags, PvSeg* pv, PvBuf B, uint32_t cap, uint32_t* tot, uint32_t* part,
-                       uint32_t jumps, hipStream_t st,
-                       hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                       uint32_t* rest);
-hipError_t launch_pvt(SEv* recs, const sg_event* ev, const uint32_t* vals, Seg* segs, const uint32_t* list, uint32_t m,
-                      const DevState& S, const DevCfg& cfg, uint32_t* dec, uint32_t* bflags, PvSeg* pv, PvBuf B,
-                      uint32_t cap, uint32_t* tot, uint32_t* hist, uint32_t* part, hipStream_t st,
-                      hipError_t (*radix_hist)(const uint32_t*, uint64_t, const uint32_t*, int, uint32_t*, uint32_t, hipStream_t),
-                      hipError_t (*radix_scatter)(const uint32_t*, const uint32_t*, uint64_t, const uint32_t*, int,
-                                                      const uint32_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t),
-                      hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                      uint32_t tile, uint32_t* rest);
-hipError_t launch_pq_mix(int post, SEv* recs, const sg_event* ev, const uint32_t* vals, const Seg* segs,
-                         const uint32_t* list, uint32_t n_narrow, uint64_t wide_off, uint32_t n_wide, const DevState& S,
-                         const DevCfg& cfg, int64_t t0, uint32_t* dec, uint32_t* bflags, hipStream_t st,
-                         const uint32_t* rest, const uint32_t* rest_n);
-hipError_t launch_seg_order(Seg* segs, const uint32_t* mp, uint32_t mb, const uint32_t* off, uint32_t* order,
-                            uint32_t* bin_off, hipStream_t st);
-hipError_t launch_gather(const SEv* rec_o, const uint32_t* vals, const uint32_t* skeys, uint64_t n,
-                         const uint32_t* pos_of, SEv* recs, uint32_t* prev, uint32_t* nprev, Link* link, uint32_t* bst,
-                         uint32_t epoch, uint32_t* bflags, hipStream_t st);
-hipError_t launch_fill(const Span* spans, const uint32_t* nspan, uint32_t cap, const SEv* recs, const Prog* prog,
-                       const DRule* rules, uint32_t* dec, hipStream_t st);
-hipError_t launch_resolve(const uint32_t* prev, uint32_t np, const uint8_t* ring, SEv* recs, const uint32_t* vals,
-                          const sg_event_ext* ext, hipStream_t st);
-hipError_t launch_ublk_words(SEv* recs, const Seg* segs, const uint32_t* order, uint32_t m, uint32_t* dec,
-                             uint32_t* cnt, const uint32_t* emb, uint32_t* ecnt, hipStream_t st);
-hipError_t launch_emb_count(const sg_event* ev, const sg_event_ext* ext, uint64_t n, uint32_t max_res, uint32_t max_ctx,
-                            const Prog* prog, const NodeInfo* info, const AuthDesc* auth, const uint32_t* auth_ids,
-                            int32_t switch_on, uint32_t* cnt, uint32_t* part, uint32_t* total, hipStream_t st);
-hipError_t launch_emb_scatter(const sg_event* ev, const sg_event_ext* ext, uint64_t n, uint32_t max_res, uint32_t max_ctx,
-                              const Prog* prog, const NodeInfo* info, const AuthDesc* auth, const uint32_t* auth_ids,
-                              int32_t switch_on, const uint32_t* off, const int64_t* flow_of, uint32_t cap,
-                              sg_token_req* req, uint32_t* idx, hipStream_t st);
-hipError_t launch_emb_answers(const sg_token_result* res, const uint32_t* idx, uint32_t nreq, const uint32_t* pos_of,
-                              const uint32_t* words, const uint32_t* P, uint32_t nhot, uint64_t n, uint32_t* side,
-                              uint32_t* stat, hipStream_t st);
-hipError_t launch_post_w(const uint32_t* words, const uint32_t* P, uint32_t nhot, const uint32_t* dec, uint64_t n,
-                         uint64_t gbase, uint8_t* ring, uint64_t ring_mask, uint32_t* out, hipStream_t st);
-hipError_t launch_post(const uint32_t* pos_of, const uint32_t* dec, uint64_t n, uint64_t gbase, uint8_t* ring,
-                       uint64_t ring_mask, uint32_t* out, hipStream_t st);
-hipError_t launch_chain(const SEv* recs, const uint32_t* vals, const Seg* segs, uint32_t m, NodeInfo* info,
-                        uint32_t grant_all, uint32_t* ncand, uint64_t* cand, const sg_event* ev, const Prog* prog,
-                        const sg_event_ext* ext, uint32_t max_ctx, hipStream_t st);
-hipError_t launch_tiny(const sg_event* ev, uint32_t n, const DevState& S, const DevCfg& cfg, uint32_t max_res,
-                       uint32_t* prio_w, const uint32_t* comp, uint64_t n_args, uint32_t grant_all,
-                       unsigned long long* pool_next, uint64_t pool_nb, uint32_t epoch, SEv* recs, uint32_t* vals,
-                       uint32_t* dec, Seg* segs, uint32_t* bflags, uint32_t* out, hipStream_t st);
-uint32_t tiny_max();
-hipError_t launch_decide_bin(int bin, const SEv* recs, const sg_event* ev, const uint32_t* vals, const Seg* segs,
-                             const uint32_t* order, uint32_t m, const DevState& S, const DevCfg& cfg, int64_t t0,
-                             uint32_t* dec, uint32_t* bflags, hipStream_t st);
-// cluster.hip
-hipError_t launch_tok_classify(const sg_token_req* req, uint64_t n, const CSlot* tab, uint32_t mask, uint32_t* fidx,
-                               sg_token_result* res, uint32_t* flags, uint32_t* nskeys, uint32_t* nsvals, uint32_t nns,
-                               hipStream_t st);
-hipError_t launch_tok_limiter_ns(const sg_token_req* req, uint64_t n, const uint32_t* sk, const uint32_t* sv,
-                                 const uint32_t* fidx, uint32_t nflows, NsLimiter* lims, const double* limits,
-                                 uint32_t nns, uint32_t* keys, uint32_t* vals, sg_token_result* res, uint32_t* bflag,
-                                 uint32_t* bidx, uint32_t* bstart, uint32_t* kpass, uint32_t* part, uint32_t* small,
-                                 uint32_t* nsb,
-                                 hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                                 hipStream_t st);
-hipError_t launch_tok_limiter_par(const sg_token_req* req, uint64_t n, const uint32_t* fidx, uint32_t nflows,
-                                  NsLimiter* lim, double allowed, uint32_t* keys, uint32_t* vals, sg_token_result* res,
-                                  uint32_t* bflag, uint32_t* cflag, uint32_t* bidx, uint32_t* cexcl, uint32_t* bstart,
-                                  uint32_t* kpass, uint32_t* part, uint32_t* small,
-                                  hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                                  hipStream_t st);
-hipError_t launch_tok_limiter(const sg_token_req* req, uint64_t n, const uint32_t* fidx, uint32_t nflows,
-                              NsLimiter* lim, double allowed, uint32_t* keys, uint32_t* vals, sg_token_result* res,
-                              hipStream_t st);
-hipError_t launch_tok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_token_req* req,
-                           CFlow* flows, uint32_t nflows, CBkt* bkts, double exceed, double max_occ_ratio,
-                           sg_token_result* res, uint32_t* bounds, uint32_t light, uint32_t wide, hipStream_t st,
-                           hipStream_t hs, hipEvent_t fork, hipEvent_t join);
-hipError_t launch_ptok_flow(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
-                            const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
-                            uint32_t mask, sg_token_result* res, uint32_t* flags, const uint32_t* serial,
-                            unsigned long long* ctr, hipStream_t st);
-hipError_t launch_ptok_prep(const sg_param_token_req* preq, uint64_t n, uint64_t n_values, sg_token_req* treq,
-                            unsigned long long* st, hipStream_t s);
-hipError_t launch_ptok_elig(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
-                            const PFlow* flows, uint32_t nflows, uint32_t* serial, hipStream_t st);
-hipError_t launch_ptok_vp(const uint32_t* skeys, const uint32_t* svals, uint64_t n, const sg_param_token_req* req,
-                          const uint64_t* values, PFlow* flows, uint32_t nflows, const PHot* hot, PVal* tab,
-                          uint32_t mask, const uint32_t* serial, uint32_t* dedup, uint32_t dmask, uint32_t* slotof,
-                          uint32_t* rep, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, int64_t* dts,
-                          int32_t* dacq, uint32_t* hist, uint32_t* part, uint32_t tile, sg_token_result* res,
-                          uint32_t* flags, unsigned long long* ctr,
-                          hipError_t (*rhist)(const uint32_t*, uint64_t, int, uint32_t*, uint32_t, hipStream_t),
-                          hipError_t (*rscatter)(const uint32_t*, const uint32_t*, uint64_t, int, const uint32_t*, uint32_t,
-                                                 uint32_t*, uint32_t*, uint32_t*, hipStream_t),
-                          hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                          hipStream_t st);
-hipError_t launch_pv_rehash(const PVal* src, uint64_t n_src, const PFlow* flows, uint32_t nflows, PVal* dst,
-                            uint32_t dmask, uint32_t* out, hipStream_t st);
-// cmetrics.hip
-uint32_t cm_chunk();
-hipError_t launch_cm_rows(const CFlow* cflows, uint32_t ncf, const CBkt* bkts, const PFlow* pflows, uint32_t npf,
-                          int64_t now, uint32_t* mask, sg_cluster_metric* rows, sg_cluster_metric* prows,
-                          hipStream_t st);
-hipError_t launch_cm_scan(const PVal* tab, uint64_t n_slots, const PFlow* flows, uint32_t nflows, const uint32_t* mask,
-                          uint32_t* cflow, uint32_t* cidx, int64_t* csum, uint64_t* ckey, uint32_t cap, uint32_t* cnt,
-                          hipStream_t st);
-hipError_t launch_cm_select(const uint32_t* skeys, const uint32_t* svals, uint32_t n, const PFlow* flows, uint32_t nflows,
-                            const int64_t* csum, const uint64_t* ckey, uint32_t top_n, uint32_t* bounds, uint32_t* nch,
-                            uint32_t* coff, uint32_t* part, int64_t* psum, uint64_t* pkey, sg_cluster_metric* prows,
-                            hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                            hipEvent_t* ev, hipStream_t st);
-// keysweep.hip
-hipError_t launch_keysweep(const PMap* pmap, uint32_t nm, const PBucket* pbkt, uint64_t pool_nb, const uint64_t* pbm,
-                           uint64_t bm_words, const uint64_t* key_ring, uint64_t ring_n, const PVal* pvtab,
-                           uint64_t pv_n, const uint64_t* tkey, const uint32_t* tidx, uint32_t tmask, uint32_t* marks,
-                           hipEvent_t* ev, hipStream_t st);
-} // namespace sg
 
 using namespace sg;
 
@@ -531,6 +308,15 @@ template <class T> void dfree(T*& p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+// a buffer that holds too little: freed, and allocated again for max(need, floor) elements of elem bytes
+template <class T> hipError_t grow(T*& p, uint64_t& cap, uint64_t need, uint64_t floor, size_t elem = sizeof(T)) {
+    dfree(p);
+    cap = 0;
+    const uint64_t c = std::max(need, floor);
+    const hipError_t rc = hipMalloc(&p, c * elem);
+    if (rc == hipSuccess) cap = c;
+    return rc;
+}
 
 } // namespace
 
@@ -597,8 +383,7 @@ struct sg_engine {
     uint32_t rules_cap = 0, hot_cap = 0;
 
     // batch scratch: two slots, so that the group stage of batch k+1 (on gstream) runs while the
-    // decide stage of batch k (on stream) is still in flight.  The d_* fields below alias the slot
-    // being filled (activate()).
+    // decide stage of batch k (on stream) is still in flight.  Every user of these arrays is handed its slot.
     struct BatchSlot {
         sg_event* d_ev = nullptr;
         uint32_t* d_out = nullptr;
@@ -609,18 +394,17 @@ struct sg_engine {
         uint32_t* d_ccnt = nullptr;    // hot / cold group stage: per-tile cold counts, the cold segments' tile scratch
         bool radix = false;            // this batch took the radix group stage (d_posof), else the hot / cold one
         uint32_t nhot = 0;             // ... with these hot ids (its words and P in d_flag / d_pos)
-        uint32_t hot_marked = 0;       // ... of which k_seg_bin marked this many for the side tables (d_bsmall[73])
-        uint32_t ublk_coop = 0, ublk_lane = 0;  // PM_UBLK segments in cooperative / lane bins (d_bsmall[74], [75])
+        uint32_t hot_marked = 0;       // ... of which k_seg_bin marked this many for the side tables (BS_HOT_MARKED)
+        uint32_t ublk_coop = 0, ublk_lane = 0;  // PM_UBLK segments in cooperative / lane bins (BS_UBLK, BS_UBLK_LANE)
         uint32_t emb_ub = 0, emb_coop = 0, emb_lane = 0;  // XF_EMB segments: their events (an upper bound of the batch's
-                                                          // token requests), those in cooperative / lane bins ([83..85])
+                                                          // token requests), those in cooperative / lane bins (BS_EMB ..)
         Seg* d_segs = nullptr;
         uint64_t* d_cand = nullptr;
-        uint32_t* d_bsmall = nullptr;  // [0] bflags [1] nseg [2] ncand [3] nprev [4..5] t0 [8..8+N_BINS] bin offsets
-                                       // [120] frozen spans recorded
+        uint32_t* d_bsmall = nullptr;  // the batch's small words (dev_types.h BS_*)
         sg_event_ext* d_ext = nullptr; // sg_submit_ex host inputs staged in HBM
         sg_arg* d_args = nullptr;
         uint64_t ext_cap = 0, args_cap = 0;
-        // sg_submit_ex: the aux.hip post-pass lists k_seg_bin builds (counts in d_bsmall[130..133])
+        // sg_submit_ex: the aux.hip post-pass lists k_seg_bin builds (counts at BS_AUX)
         uint32_t* d_ashort = nullptr;
         uint64_t *d_apiece = nullptr, *d_amulti = nullptr, *d_along = nullptr;
         uint64_t aux_cap_n = 0;
@@ -634,9 +418,9 @@ struct sg_engine {
                                          // fill the slot waits for it on the device
         hipEvent_t lent = nullptr;       // the slot's arrays were the scratch of the other slot's embedded token call,
                                          // which ends here on the engine stream: the next group stage waits for it too
-        uint32_t* h_head = nullptr;    // pinned: d_bsmall[0..77) as the group stage left it (copied on gstream)
+        uint32_t* h_head = nullptr;    // pinned: d_bsmall[0..BS_HEAD_WORDS) as the group stage left it (copied on gstream)
         // What the decide stage needs of the group part's locals: it may run inside the next submit, after
-        // e->gbase, e->epoch and the d_* aliases have moved on, so nothing of these is re-read from the engine.
+        // e->gbase and e->epoch have moved on, so nothing of these is re-read from the engine.
         struct Grouped {
             uint64_t n = 0, n_args = 0, gbase = 0, ring_mask = 0;
             const sg_event* dev_ev = nullptr;
@@ -659,7 +443,7 @@ struct sg_engine {
     // being collected, and the one before that, whose end events the collected batch's gaps are measured from.
     static constexpr int N_SETS = 4;
     hipEvent_t evset[N_SETS][5] = {};
-    uint32_t* h_mirror = nullptr;  // pinned, N_SETS x MIRROR_WORDS: d_bsmall[0..121) as the decide stage left it
+    uint32_t* h_mirror = nullptr;  // pinned, N_SETS x BS_MIRROR_WORDS of d_bsmall as the decide stage left it
     uint64_t seq = 0;              // batches handed to the decide stage so far (batch i has set i % N_SETS)
     struct InFlight { int set; uint32_t hot_marked, ublk_coop, ublk_lane, emb_coop, emb_lane; };
     std::deque<InFlight> inflight;  // handed off, not yet collected (timings, flags), oldest first
@@ -729,29 +513,14 @@ struct sg_engine {
     bool auth_on = false, auth_loaded = false;
     std::vector<std::string> last_auth;
     uint32_t* d_comp = nullptr;  // [res] STRATEGY_RELATE component representative (sort key); null: none
-    uint32_t* d_prev = nullptr;
-    uint32_t* d_bsmall = nullptr;
-    Link* d_link = nullptr;
-    uint32_t *d_bst = nullptr, *d_pend = nullptr;
-    Span* d_spans = nullptr;
     uint32_t span_cap = 0;
     uint32_t epoch = 0;          // link tag of the batch being grouped
     uint64_t spans_total = 0;    // frozen span slots taken by the cooperative kernels (diagnostics)
-    uint64_t cap_n = 0;
-    sg_event* d_ev = nullptr;
-    uint32_t* d_out = nullptr;
-    uint32_t *d_k0 = nullptr, *d_v0 = nullptr, *d_k1 = nullptr, *d_v1 = nullptr;
-    uint32_t *d_hist = nullptr, *d_part = nullptr, *d_flag = nullptr, *d_pos = nullptr, *d_order = nullptr;
-    uint32_t *d_posof = nullptr, *d_dec = nullptr, *d_blkcnt = nullptr;
-    SEv *d_recs = nullptr, *d_rec_o = nullptr;
-    Seg* d_segs = nullptr;
-    // d_small: [0] bflags [1] nseg [2] ncand [3] snapshot total [8..8+N_BINS) bin counts
-    //          [64..64+N_BINS) bin cursors
-    uint32_t* d_small = nullptr;
+    uint64_t cap_n = 0;          // events both slots' arrays hold (ensure_batch)
+    uint32_t* d_small = nullptr;  // the engine's small words (dev_types.h SM_*)
     uint32_t* d_sink = nullptr;  // 1024 words, DevState.sink
     int64_t* d_borrow = nullptr;  // [res][2]{ws, pass}: second-window borrow rings (prioritized entries)
     uint64_t* d_keyring = nullptr;  // ENTRY arg keys by global index (exit(count, args)); once param rules exist
-    uint64_t* d_cand = nullptr;
     uint32_t dbg_flags = 0;
     int prof_bin = 0;            // SG_PROF_BIN: which cooperative bin (0 J16, 1 J4, 2 J1) fills the SG_DEBUG counters
     unsigned long long* d_dbg = nullptr;  // SG_DEBUG=1: [0..63] counters of the J16 bin
@@ -826,7 +595,7 @@ struct sg_engine {
     sg_token_result* d_tres = nullptr;
     uint32_t* d_tfidx = nullptr;
     uint32_t* d_tbounds = nullptr;  // the flows' first sorted positions (nflows + 1 words)
-    uint32_t tbounds_cap = 0;
+    uint64_t tbounds_cap = 0;
     uint64_t tcap = 0;
     // cluster param flows (ClusterParamFlowRuleManager / ClusterParamMetricStatistics roles)
     std::vector<PFlow> pflows;                    // host copy of the config part
@@ -893,31 +662,14 @@ namespace {
 
 constexpr uint64_t SHARD_BATCH = 3ull << 21;  // batches of fewer events take the shard-sized bins and skip threshold
 
-static void activate(sg_engine* e, int k) {
-    auto& B = e->slot[k];
-    e->d_ev = B.d_ev; e->d_out = B.d_out;
-    e->d_k0 = B.d_k0; e->d_v0 = B.d_v0; e->d_k1 = B.d_k1; e->d_v1 = B.d_v1;
-    e->d_hist = B.d_hist; e->d_part = B.d_part; e->d_flag = B.d_flag; e->d_pos = B.d_pos; e->d_order = B.d_order;
-    e->d_posof = B.d_posof; e->d_dec = B.d_dec; e->d_blkcnt = B.d_blkcnt; e->d_prev = B.d_prev;
-    e->d_recs = B.d_recs; e->d_rec_o = B.d_rec_o; e->d_segs = B.d_segs; e->d_cand = B.d_cand;
-    e->d_bsmall = B.d_bsmall;
-    e->d_link = B.d_link; e->d_bst = B.d_bst; e->d_pend = B.d_pend; e->d_spans = B.d_spans;
-}
 static void free_slot(sg_engine::BatchSlot& B) {
     dfree(B.d_ev); dfree(B.d_out); dfree(B.d_k0); dfree(B.d_v0); dfree(B.d_k1); dfree(B.d_v1);
     dfree(B.d_hist); dfree(B.d_part); dfree(B.d_flag); dfree(B.d_pos); dfree(B.d_order); dfree(B.d_segs);
     dfree(B.d_cand); dfree(B.d_posof); dfree(B.d_dec); dfree(B.d_recs); dfree(B.d_rec_o); dfree(B.d_blkcnt);
     dfree(B.d_prev); dfree(B.d_bsmall); dfree(B.d_ccnt);
-    B.d_ccnt = nullptr;
     dfree(B.d_link); dfree(B.d_bst); dfree(B.d_pend); dfree(B.d_spans); dfree(B.d_ext); dfree(B.d_args);
     dfree(B.d_ashort); dfree(B.d_apiece); dfree(B.d_amulti); dfree(B.d_along); dfree(B.d_mix);
-    B.d_mix = nullptr;
     B.ext_cap = B.args_cap = B.aux_cap_n = B.mix_cap = 0;
-    B.d_link = nullptr; B.d_bst = B.d_pend = nullptr; B.d_spans = nullptr;
-    B.d_ev = nullptr; B.d_out = nullptr; B.d_k0 = B.d_v0 = B.d_k1 = B.d_v1 = nullptr;
-    B.d_hist = B.d_part = B.d_flag = B.d_pos = B.d_order = nullptr;
-    B.d_posof = B.d_dec = B.d_blkcnt = B.d_prev = B.d_bsmall = nullptr;
-    B.d_recs = B.d_rec_o = nullptr; B.d_segs = nullptr; B.d_cand = nullptr;
 }
 int ensure_batch(sg_engine* e, uint64_t n) {
     if (n <= e->cap_n) return SG_OK;
@@ -960,8 +712,8 @@ int ensure_batch(sg_engine* e, uint64_t n) {
     for (auto& B : e->slot) {
         HIPCHK(hipMalloc(&B.d_blkcnt, ((c + 255) / 256 + 1) * N_BINS * 4));
         HIPCHK(hipMalloc(&B.d_prev, c * 4));
-        HIPCHK(hipMalloc(&B.d_bsmall, 256 * 4));
-        HIPCHK(hipMemset(B.d_bsmall, 0, 256 * 4));
+        HIPCHK(hipMalloc(&B.d_bsmall, BS_WORDS * 4));
+        HIPCHK(hipMemset(B.d_bsmall, 0, BS_WORDS * 4));
         HIPCHK(hipMalloc(&B.d_link, c * sizeof(Link)));
         HIPCHK(hipMemset(B.d_link, 0, c * sizeof(Link)));  // tag 0 is never a batch's epoch
         HIPCHK(hipMalloc(&B.d_bst, ((c + 1023) / 1024 + 1) * 4));
@@ -970,13 +722,43 @@ int ensure_batch(sg_engine* e, uint64_t n) {
     }
     e->span_cap = (uint32_t)(c / SPAN_CHUNK + 65536);
     e->cap_n = c;
-    activate(e, e->cur);
     return SG_OK;
 }
 
-constexpr uint32_t HEAD_WORDS = 86;     // d_bsmall words the host reads after the group stage
-constexpr uint32_t MIRROR_WORDS = 121;  // ... and after the decide stage ([0] bflags, [119] RF_UBLK words written,
-                                        // [120] frozen spans)
+// What a batch's flags say of it, in two steps.  The group stage's checks: a batch that fails one is rejected before
+// any decision.
+static int group_verdict(uint32_t bflags) {
+    if (bflags & BF_BAD_RES) return fail(SG_EINVAL, "event res_id >= max_resources");
+    if (bflags & BF_BAD_REF)
+        return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
+    if (bflags & BF_TSPAN) return fail(SG_EINVAL, "a batch must span less than 2^31 ms");
+    if (bflags & BF_BACKWARD) return fail(SG_EINVAL, "event timestamps must be non-decreasing (SURVEY Q3)");
+    if (bflags & BF_BAD_ARGS)
+        return fail(SG_EINVAL, "an sg_event_ext names args outside the table (or more than SG_MAX_ARGS, or a bad kind)");
+    return SG_OK;
+}
+// Flags the decide kernels raise (the group stage's own checks return before the decide stage runs):
+// an EXIT/TRACE whose reference names an event that is not an earlier ENTRY of its resource, and a
+// batch starting before the last window a resource already holds (the clock went back).
+static int decide_verdict(sg_engine* e, uint32_t bflags) {
+    if (bflags & BF_BAD_REF)
+        return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
+    if (bflags & BF_BACKWARD)
+        return fail(SG_EINVAL, "event timestamps must be non-decreasing across batches (SURVEY Q3)");
+    if (bflags & BF_AUX_FULL) return fail(SG_ECAPACITY, "origin/context node pool full (raise aux_node_capacity)");
+    if (bflags & BF_LITE_STALE)
+        return fail(SG_ESTATE, "internal error (SG_LITE_CHECK): k_lite stored a minute bucket without a load that was not stale");
+    // A map that could not place a key has already committed its ring bit and live count (a ghost entry), and a
+    // failed k_pq invariant leaves its maps in an unknown state: the engine refuses every later batch.
+    if (bflags & BF_PQ_INVARIANT)
+        e->fatal = "internal error: a k_pq tile's presorted key subset did not match its accesses";
+    else if (bflags & BF_POOL_FULL)  // a map that could not grow may have lost a key (a ghost entry, as below)
+        e->fatal = "the hot-parameter map pool is used up (raise param_table_log2)";
+    else if (bflags & BF_PTAB_FULL)
+        e->fatal = "a hot-parameter map table could not place a key (its map holds a ghost entry)";
+    if (bflags & (BF_PQ_INVARIANT | BF_PTAB_FULL | BF_POOL_FULL)) return fail(SG_ECAPACITY, e->fatal + " -- engine unusable");
+    return SG_OK;
+}
 
 // The oldest batch in flight: wait for its decide stage, record its stage times and the idle time of both streams
 // before it, and check its device flags (from the pinned mirror its decide stage filled: nothing is enqueued here).
@@ -1007,19 +789,19 @@ static int collect(sg_engine* e) {
     }
     e->glog.push_back({(double)ga, (double)gb});
     if (e->glog.size() > 4096) e->glog.erase(e->glog.begin(), e->glog.begin() + 2048);
-    const uint32_t* mir = e->h_mirror + (size_t)f.set * MIRROR_WORDS;
-    const uint32_t bflags = mir[0];
-    e->spans_total += mir[120];
+    const uint32_t* mir = e->h_mirror + (size_t)f.set * BS_MIRROR_WORDS;
+    const uint32_t bflags = mir[BS_FLAGS];
+    e->spans_total += mir[BS_NSPAN];
     e->hot_marked_last = f.hot_marked;
     e->ublk_last[0] = f.ublk_coop;
     e->ublk_last[1] = f.ublk_lane;
-    e->ublk_last[2] = mir[119];
-    // the embedded token server's read-back: [100] requests, [101..107] answers by class, [108] words written ahead
-    for (int i = 0; i < 9; ++i) e->emb_last[i] = mir[100 + i];
+    e->ublk_last[2] = mir[BS_UBLK_WORDS];
+    // the embedded token server's read-back: BS_EMB_REQ .. BS_EMB_AHEAD (requests, answers by class, words written ahead)
+    for (int i = 0; i < 9; ++i) e->emb_last[i] = mir[BS_EMB_REQ + i];
     e->emb_last[9] = f.emb_coop;
     e->emb_last[10] = f.emb_lane;
     e->emb_last[11] = 0;  // (no late lane pass: rules with cluster_fallback_to_local are refused)
-    if (e->emb_timed && mir[100]) {  // (the batch's events are done: its post end was waited for above)
+    if (e->emb_timed && mir[BS_EMB_REQ]) {  // (the batch's events are done: its post end was waited for above)
         for (int i = 0; i < 3; ++i) {
             float ms = 0;
             (void)hipEventElapsedTime(&ms, e->emb_t[i], e->emb_t[i + 1]);
@@ -1028,26 +810,7 @@ static int collect(sg_engine* e) {
         (void)hipGetLastError();
         e->emb_timed = false;
     }
-    // Flags the decide kernels raise (the group stage's own checks return before the decide stage runs):
-    // an EXIT/TRACE whose reference names an event that is not an earlier ENTRY of its resource, and a
-    // batch starting before the last window a resource already holds (the clock went back).
-    if (bflags & BF_BAD_REF)
-        return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
-    if (bflags & BF_BACKWARD)
-        return fail(SG_EINVAL, "event timestamps must be non-decreasing across batches (SURVEY Q3)");
-    if (bflags & BF_AUX_FULL) return fail(SG_ECAPACITY, "origin/context node pool full (raise aux_node_capacity)");
-    if (bflags & BF_LITE_STALE)
-        return fail(SG_ESTATE, "internal error (SG_LITE_CHECK): k_lite stored a minute bucket without a load that was not stale");
-    // A map that could not place a key has already committed its ring bit and live count (a ghost entry), and a
-    // failed k_pq invariant leaves its maps in an unknown state: the engine refuses every later batch.
-    if (bflags & BF_PQ_INVARIANT)
-        e->fatal = "internal error: a k_pq tile's presorted key subset did not match its accesses";
-    else if (bflags & BF_POOL_FULL)  // a map that could not grow may have lost a key (a ghost entry, as below)
-        e->fatal = "the hot-parameter map pool is used up (raise param_table_log2)";
-    else if (bflags & BF_PTAB_FULL)
-        e->fatal = "a hot-parameter map table could not place a key (its map holds a ghost entry)";
-    if (bflags & (BF_PQ_INVARIANT | BF_PTAB_FULL | BF_POOL_FULL)) return fail(SG_ECAPACITY, e->fatal + " -- engine unusable");
-    return SG_OK;
+    return decide_verdict(e, bflags);
 }
 // every batch in flight done (called by the API functions that read or write engine state)
 // the authority table the kernels read: null unless authority rules are loaded (the kernels then run as without)
@@ -1418,10 +1181,10 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
                 DevState Sg{};
                 std::memset(&Sg, 0, sizeof(Sg));
                 Sg.pmap = e->d_pmap; Sg.pbkt = e->d_pbkt; Sg.pdat = e->d_pdat; Sg.pbm = e->d_pbm;
-                HIPCHK(hipMemset(e->d_small, 0, 4));
-                HIPCHK(launch_pm_grow_ids(d_ids, (uint32_t)ids.size(), Sg, e->d_pool_next, e->pool_nb, e->d_small, e->stream));
+                HIPCHK(hipMemset(e->d_small + SM_FLAGS, 0, 4));
+                HIPCHK(launch_pm_grow_ids(d_ids, (uint32_t)ids.size(), Sg, e->d_pool_next, e->pool_nb, e->d_small + SM_FLAGS, e->stream));
                 uint32_t fl = 0;
-                HIPCHK(hipMemcpyAsync(&fl, e->d_small, 4, hipMemcpyDeviceToHost, e->stream));
+                HIPCHK(hipMemcpyAsync(&fl, e->d_small + SM_FLAGS, 4, hipMemcpyDeviceToHost, e->stream));
                 HIPCHK(hipStreamSynchronize(e->stream));
                 (void)hipFree(d_ids);
                 if (fl & (BF_POOL_FULL | BF_PTAB_FULL))
@@ -1462,7 +1225,6 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
     e->has_multi = any_multi;
     if (comp.empty()) {
         dfree(e->d_comp);
-        e->d_comp = nullptr;
     } else {
         if (!e->d_comp) HIPCHK(hipMalloc(&e->d_comp, (uint64_t)R * 4));
         HIPCHK(hipMemcpy(e->d_comp, comp.data(), (uint64_t)R * 4, hipMemcpyHostToDevice));
@@ -1596,16 +1358,16 @@ int sg_engine_create(const sg_config* cfg_in, sg_engine** out) {
     for (auto& s : e->evset)
         for (auto& v : s) if (hipEventCreate(&v) != hipSuccess) return bad(fail(SG_EDEVICE, "event"));
     for (auto& B : e->slot) {
-        if (hipHostMalloc(&B.h_head, HEAD_WORDS * 4) != hipSuccess) return bad(fail(SG_ENOMEM, "pinned batch head"));
+        if (hipHostMalloc(&B.h_head, BS_HEAD_WORDS * 4) != hipSuccess) return bad(fail(SG_ENOMEM, "pinned batch head"));
         B.ev = e->evset[0];
     }
-    if (hipHostMalloc(&e->h_mirror, sg_engine::N_SETS * MIRROR_WORDS * 4) != hipSuccess)
+    if (hipHostMalloc(&e->h_mirror, sg_engine::N_SETS * BS_MIRROR_WORDS * 4) != hipSuccess)
         return bad(fail(SG_ENOMEM, "pinned batch flags"));
-    std::memset(e->h_mirror, 0, sg_engine::N_SETS * MIRROR_WORDS * 4);
+    std::memset(e->h_mirror, 0, sg_engine::N_SETS * BS_MIRROR_WORDS * 4);
     uint64_t R = cfg.max_resources;
     if (hipMalloc(&e->d_sec, R * 2 * sizeof(Bkt)) != hipSuccess || hipMalloc(&e->d_minb, R * 60 * sizeof(Bkt)) != hipSuccess ||
         hipMalloc(&e->d_info, R * sizeof(NodeInfo)) != hipSuccess || hipMalloc(&e->d_prog, R * sizeof(Prog)) != hipSuccess ||
-        hipMalloc(&e->d_ring, 1ull << cfg.status_ring_log2) != hipSuccess || hipMalloc(&e->d_small, 256 * 4) != hipSuccess ||
+        hipMalloc(&e->d_ring, 1ull << cfg.status_ring_log2) != hipSuccess || hipMalloc(&e->d_small, SM_WORDS * 4) != hipSuccess ||
         hipMalloc(&e->d_sink, 1024 * 4) != hipSuccess || hipMalloc(&e->d_borrow, R * 4 * sizeof(int64_t)) != hipSuccess ||
         hipMalloc(&e->d_prio, R * 4) != hipSuccess || hipMalloc(&e->d_hot_tab, R * 2) != hipSuccess ||
         hipMalloc(&e->d_hot_list, hot_max() * 4) != hipSuccess)
@@ -2097,7 +1859,6 @@ static int rebuild_cluster(sg_engine* e, const sg_flow_rule* rules, uint32_t n) 
         tab[h].pad = ns_index(e, nf[i].flow_id);
     }
     dfree(e->d_cflow); dfree(e->d_cbkt); dfree(e->d_ctab);
-    e->d_cflow = nullptr; e->d_cbkt = nullptr; e->d_ctab = nullptr;
     if (!nf.empty()) {
         HIPCHK(hipMalloc(&e->d_cflow, nf.size() * sizeof(CFlow)));
         HIPCHK(hipMemcpy(e->d_cflow, nf.data(), nf.size() * sizeof(CFlow), hipMemcpyHostToDevice));
@@ -2209,8 +1970,7 @@ static int upload_authority(sg_engine* e) {
         return fail(SG_ENOMEM, "device allocation of the authority table failed");
     const size_t ni = std::max<size_t>(1, e->auth.ids.size());
     if (ni > e->auth_ids_cap) {
-        if (e->d_auth_ids) (void)hipFree(e->d_auth_ids);
-        e->d_auth_ids = nullptr;
+        dfree(e->d_auth_ids);
         e->auth_ids_cap = 0;
         if (hipMalloc(&e->d_auth_ids, 2 * ni * sizeof(uint32_t)) != hipSuccess)
             return fail(SG_ENOMEM, "device allocation of the authority id lists failed");
@@ -2394,7 +2154,6 @@ static int rebuild_cluster_param(sg_engine* e, const sg_param_rule* rules, const
         tab[h].pad = ns_index(e, nf[i].flow_id);
     }
     dfree(e->d_pflow); dfree(e->d_phot); dfree(e->d_pftab);
-    e->d_pflow = nullptr; e->d_phot = nullptr; e->d_pftab = nullptr;
     if (!nf.empty()) {
         HIPCHK(hipMalloc(&e->d_pflow, nf.size() * sizeof(PFlow)));
         HIPCHK(hipMemcpy(e->d_pflow, nf.data(), nf.size() * sizeof(PFlow), hipMemcpyHostToDevice));
@@ -2595,7 +2354,7 @@ static int compact_pmaps(sg_engine* e) {
     hipStream_t st = e->stream;
     HIPCHK(hipMemsetAsync(e->d_pbkt2, 0xFF, e->pool_nb * sizeof(PBucket), st));  // PK_EMPTY: regions grow into it
     HIPCHK(launch_pm_compact(e->d_pmap, nm, e->d_pbkt, e->d_pdat, e->d_pbkt2, e->d_pdat2, e->d_pcwork,
-                             e->d_pcwork + e->pmoves_cap, e->d_pcwork + 2 * e->pmoves_cap, e->d_pool_next, launch_scan, st));
+                             e->d_pcwork + e->pmoves_cap, e->d_pcwork + 2 * e->pmoves_cap, e->d_pool_next, st));
     HIPCHK(hipMemcpyAsync(e->h_pool_next, e->d_pool_next, PC_WORDS * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     std::swap(e->d_pbkt, e->d_pbkt2);
@@ -2749,7 +2508,6 @@ static void free_pv(sg_engine* e) {
     free_pvbuf(e->pvb);
     free_pvbuf(e->pvbt);
     dfree(e->d_pvhist); dfree(e->d_pvpart); dfree(e->d_pvthist); dfree(e->d_pvtpart);
-    e->d_pvhist = e->d_pvpart = e->d_pvthist = e->d_pvtpart = nullptr;
     e->pv_cap = 0;
     e->pvch_cap = 0;
 }
@@ -2813,11 +2571,7 @@ static int ensure_pv(sg_engine* e, uint64_t cap, uint64_t m) {
 
 // The XF_MIX segment lists of slot B for up to mb segments (narrow, then wide at mix_cap)
 static int ensure_mix(sg_engine::BatchSlot& B, uint64_t mb) {
-    if (mb > B.mix_cap) {
-        dfree(B.d_mix);
-        B.mix_cap = std::max<uint64_t>(mb, 1u << 12);
-        HIPCHK(hipMalloc(&B.d_mix, B.mix_cap * 2 * 4));
-    }
+    if (mb > B.mix_cap) HIPCHK(grow(B.d_mix, B.mix_cap, mb, 1u << 12, 2 * 4));
     return SG_OK;
 }
 
@@ -2840,10 +2594,7 @@ static int ensure_aux(sg_engine* e, sg_engine::BatchSlot& B, uint64_t n) {
     }
     if (npiece > e->auxmeta_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));  // no decide stage may use the old buffer
-        dfree(e->d_auxmeta);
-        const uint64_t c = std::max<uint64_t>(npiece, B.aux_cap_n / AUX_PIECE + B.aux_cap_n / 257 + 64);
-        HIPCHK(hipMalloc(&e->d_auxmeta, c * 8));
-        e->auxmeta_cap = c;
+        HIPCHK(grow(e->d_auxmeta, e->auxmeta_cap, npiece, B.aux_cap_n / AUX_PIECE + B.aux_cap_n / 257 + 64));
     }
     return SG_OK;
 }
@@ -2852,6 +2603,73 @@ static bool is_device_ptr(const void* p) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+// sg_submit_ex: the Context and args tables in HBM, staged in slot B on stream st when the caller's are host memory
+static int stage_ext_args(sg_engine::BatchSlot& B, const sg_event_ext* ext, uint64_t n, const sg_arg* args,
+                          uint64_t n_args, hipStream_t st, const sg_event_ext** dev_ext, const sg_arg** dev_args) {
+    *dev_ext = ext;
+    *dev_args = n_args ? args : nullptr;
+    if (ext && !is_device_ptr(ext)) {
+        if (n > B.ext_cap) HIPCHK(grow(B.d_ext, B.ext_cap, n, 1u << 16));
+        HIPCHK(hipMemcpyAsync(B.d_ext, ext, n * sizeof(sg_event_ext), hipMemcpyHostToDevice, st));
+        *dev_ext = B.d_ext;
+    }
+    if (n_args && !is_device_ptr(args)) {
+        if (n_args > B.args_cap) HIPCHK(grow(B.d_args, B.args_cap, n_args, 1u << 16));
+        HIPCHK(hipMemcpyAsync(B.d_args, args, n_args * sizeof(sg_arg), hipMemcpyHostToDevice, st));
+        *dev_args = B.d_args;
+    }
+    return SG_OK;
+}
+
+// The DevCfg of a batch and what its DevState holds whichever path decides it from slot B; gbase, epoch, skip_ok and
+// skip_min are the caller's to set
+static void fill_state(const sg_engine* e, const sg_engine::BatchSlot& B, uint64_t ring_mask, const sg_event_ext* dev_ext,
+                       const sg_arg* dev_args, DevCfg& dc, DevState& S) {
+    std::memset(&dc, 0, sizeof(dc));
+    dc.max_rt = e->cfg.statistic_max_rt;
+    dc.occupy_timeout = e->cfg.occupy_timeout_ms;
+    dc.max_chain = e->cfg.max_slot_chain_size;
+    dc.switch_on = e->cfg.switch_on;
+    dc.ring_mask = ring_mask;
+    dc.snap_hi = e->snap_hi;
+    dc.dbg_flags = e->dbg_flags;
+    dc.heads = e->has_head ? 1u : 0u;
+    std::memset(&S, 0, sizeof(S));
+    S.sec = e->d_sec;
+    S.minb = e->d_minb;
+    S.info = e->d_info;
+    S.prog = e->d_prog;
+    S.rules = e->d_rules;
+    S.rstate = e->d_rstate;
+    S.hot = e->d_hot;
+    S.pmap = e->d_pmap;
+    S.pbkt = e->d_pbkt;
+    S.pdat = e->d_pdat;
+    S.pbm = e->d_pbm;
+    S.ppre = e->d_ppre;
+    S.tmid = e->d_tmid;
+    S.ring = e->d_ring;
+    S.sink = e->d_sink;
+    S.borrow = e->d_borrow;
+    S.prio = e->d_prio;
+    S.key_ring = e->d_keyring;
+    S.link = B.d_link;
+    S.bst = B.d_bst;
+    S.pend = B.d_pend;
+    S.spans = B.d_spans;
+    S.nspan = B.d_bsmall + BS_NSPAN;
+    S.span_cap = e->span_cap;
+    S.ext = dev_ext;
+    S.args = dev_args;
+    S.aux_tab = e->d_auxtab;
+    S.aux_count = e->d_auxcnt;
+    S.aux_cap = e->cfg.aux_node_capacity;
+    S.aux_mask = e->aux_mask;
+    S.max_ctx = SG_MAX_CONTEXTS;
+    S.auth = dev_auth(e);
+    S.auth_ids = dev_auth_ids(e);
 }
 
 static int decide_stage(sg_engine* e, int k);
@@ -2863,8 +2681,8 @@ static int decide_stage(sg_engine* e, int k);
 // for the host to get through those launches.  What the decide stage of this batch needs is left in B.g.
 static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_ext* ext, uint64_t n, const sg_arg* args,
                        uint64_t n_args, uint32_t* out, int* prev) {
-    activate(e, k);
     auto& B = e->slot[k];
+    uint32_t* const sw = B.d_bsmall;  // the batch's small words (BS_*)
     B.ev = e->evset[e->seq % sg_engine::N_SETS];
     hipStream_t gs = e->gstream;
     // the slot's last batch is decided and its decisions are out before anything of the slot is overwritten
@@ -2877,31 +2695,13 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
     bool host_in = !is_device_ptr(ev);
     bool host_out = !is_device_ptr(out);
     if (host_in) {
-        HIPCHK(hipMemcpyAsync(e->d_ev, ev, n * sizeof(sg_event), hipMemcpyHostToDevice, gs));
-        dev_ev = e->d_ev;
+        HIPCHK(hipMemcpyAsync(B.d_ev, ev, n * sizeof(sg_event), hipMemcpyHostToDevice, gs));
+        dev_ev = B.d_ev;
     }
-    uint32_t* dev_out = host_out ? e->d_out : out;
-    // sg_submit_ex: the Context and args tables in HBM (staged per batch slot when the caller's are host memory)
-    const sg_event_ext* dev_ext = ext;
-    const sg_arg* dev_args = n_args ? args : nullptr;
-    if (ext && !is_device_ptr(ext)) {
-        if (n > B.ext_cap) {
-            dfree(B.d_ext);
-            B.ext_cap = std::max<uint64_t>(n, 1u << 16);
-            HIPCHK(hipMalloc(&B.d_ext, B.ext_cap * sizeof(sg_event_ext)));
-        }
-        HIPCHK(hipMemcpyAsync(B.d_ext, ext, n * sizeof(sg_event_ext), hipMemcpyHostToDevice, gs));
-        dev_ext = B.d_ext;
-    }
-    if (n_args && !is_device_ptr(args)) {
-        if (n_args > B.args_cap) {
-            dfree(B.d_args);
-            B.args_cap = std::max<uint64_t>(n_args, 1u << 16);
-            HIPCHK(hipMalloc(&B.d_args, B.args_cap * sizeof(sg_arg)));
-        }
-        HIPCHK(hipMemcpyAsync(B.d_args, args, n_args * sizeof(sg_arg), hipMemcpyHostToDevice, gs));
-        dev_args = B.d_args;
-    }
+    uint32_t* dev_out = host_out ? B.d_out : out;
+    const sg_event_ext* dev_ext;
+    const sg_arg* dev_args;
+    if (int src = stage_ext_args(B, ext, n, args, n_args, gs, &dev_ext, &dev_args)) return src;
     const uint64_t ring_mask = (1ull << e->cfg.status_ring_log2) - 1;
     // Overlapping this group stage with the previous batch's decide stage wins once the decide kernels
     // no longer stream frozen stretches through single CUs (C4 on MI355X: 6.45 -> 5.45 ms per batch);
@@ -2919,8 +2719,8 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
     const int db = 8;
     int passes = (bits + db - 1) / db;
     uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
-    int64_t* d_t0 = reinterpret_cast<int64_t*>(e->d_bsmall + 4);  // [4..5]
-    uint32_t *kin = e->d_k1, *vin = e->d_v1, *kout = e->d_k0, *vout = e->d_v0;
+    int64_t* d_t0 = reinterpret_cast<int64_t*>(sw + BS_T0);
+    uint32_t *kin = B.d_k1, *vin = B.d_v1, *kout = B.d_k0, *vout = B.d_v0;
     if (++e->epoch == 0) e->epoch = 1;
     const uint32_t ublk = (e->dbg_flags & UBLK_OFF) ? 0u : 1u;
     // every event through the radix passes: SG_DEBUG_FLAGS & 8192 (A/B of the group stage), or a batch of 2^30 events
@@ -2928,7 +2728,7 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
     B.radix = e->radix_group || n >= (1ull << 30) || n < e->radix_below;
     // one launch clears the batch's small words and, for the hot / cold stage, bst[] and the side-table marks: the
     // slot's are free once its last batch is decided (above), d_need since the previous group stage on this stream
-    HIPCHK(launch_grp_clear(e->d_bsmall, 256, e->d_bst, B.radix ? 0u : (uint32_t)((n + 1023) / 1024), e->d_need,
+    HIPCHK(launch_grp_clear(B.d_bsmall, BS_WORDS, B.d_bst, B.radix ? 0u : (uint32_t)((n + 1023) / 1024), e->d_need,
                             B.radix ? 0u : (uint32_t)e->need_words, gs));
     // bins + bin-ordered dispatch list (per-block counts -> scan -> placement), sized by an upper bound of
     // the segment count so that the group stage needs one host round trip
@@ -2974,81 +2774,77 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
         if (e->has_mix) {  // the XF_MIX lists of this slot
             if (int mrc = ensure_mix(B, mb)) return mrc;
         }
-        HIPCHK(launch_seg_bin(e->d_segs, e->d_bsmall + 1, mb, n, e->d_prog, e->d_prio, lane_max, lite_max, j1_max, j4_max,
-                              force_lane ? 1 : 0, e->d_blkcnt, e->pq_on ? 1u : 0u, e->pq_wide, ext ? e->d_bsmall + 130 : nullptr,
-                              B.d_ashort, B.d_along, B.d_amulti, e->d_bsmall + 6, e->has_mix ? B.d_mix : nullptr,
-                              (uint32_t)B.mix_cap, e->d_bsmall + 72, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
-                              (e->dbg_flags & HEAD_OFF) ? 0u : e->head_min, e->d_hot_tab, e->nhot, e->d_bsmall + 80, need_hot,
-                              need_blk, bmax, skip_min, e->d_bsmall + 73, e->d_bsmall + 74, e->emb_n ? e->d_bsmall + 83 : nullptr,
-                              R, gs));
-        HIPCHK(launch_scan(e->d_blkcnt, e->d_blkcnt, (uint64_t)nblk * N_BINS, e->d_part, nullptr, gs));
-        HIPCHK(launch_seg_order(e->d_segs, e->d_bsmall + 1, mb, e->d_blkcnt, e->d_order, e->d_bsmall + 8, gs));
+        HIPCHK(launch_seg_bin(B.d_segs, sw + BS_NSEG, mb, n, e->d_prog, e->d_prio, lane_max, lite_max, j1_max, j4_max,
+                              force_lane ? 1 : 0, B.d_blkcnt, e->pq_on ? 1u : 0u, e->pq_wide, ext ? sw + BS_AUX : nullptr,
+                              B.d_ashort, B.d_along, B.d_amulti, sw + BS_MIX_N, e->has_mix ? B.d_mix : nullptr,
+                              (uint32_t)B.mix_cap, sw + BS_MIX_WIDE, (e->pv_on || e->pvt_on) ? 0u : e->pq_wide,
+                              (e->dbg_flags & HEAD_OFF) ? 0u : e->head_min, e->d_hot_tab, e->nhot, sw + BS_HOT_SEGS,
+                              need_hot, need_blk, bmax, skip_min, sw + BS_HOT_MARKED, sw + BS_UBLK,
+                              e->emb_n ? sw + BS_EMB : nullptr, R, gs));
+        HIPCHK(launch_scan(B.d_blkcnt, B.d_blkcnt, (uint64_t)nblk * N_BINS, B.d_part, nullptr, gs));
+        HIPCHK(launch_seg_order(B.d_segs, sw + BS_NSEG, mb, B.d_blkcnt, B.d_order, sw + BS_BIN_OFF, gs));
         return SG_OK;
     };
-    // the previous batch's decide stage, enqueued while this batch's first kernel runs; the d_* aliases come back
-    // to this slot afterwards
+    // the previous batch's decide stage, enqueued while this batch's first kernel runs
     auto decide_prev = [&]() -> int {
         if (*prev < 0) return SG_OK;
         const int pk = *prev;
         *prev = -1;  // (enqueued, or failed for good: the caller does not try again)
-        const int drc = decide_stage(e, pk);
-        activate(e, k);
-        return drc;
+        return decide_stage(e, pk);
     };
     if (B.radix) {
-        HIPCHK(launch_rs_first(dev_ev, n, R, e->gbase, e->d_ring, ring_mask, e->cfg.statistic_max_rt, e->d_rec_o,
-                               e->d_k1, e->d_v1, e->d_hist, nblocks, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
+        HIPCHK(launch_rs_first(dev_ev, n, R, e->gbase, e->d_ring, ring_mask, e->cfg.statistic_max_rt, B.d_rec_o,
+                               B.d_k1, B.d_v1, B.d_hist, nblocks, sw + BS_FLAGS, d_t0, e->d_prio, e->d_keyring,
                                e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e), ublk, gs));
         if (int drc = decide_prev()) return drc;
         for (int p = 0; p < passes; ++p) {
-            if (p > 0) HIPCHK(launch_radix_hist(kin, n, p * db, e->d_hist, nblocks, gs));
-            HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks << db, e->d_part, nullptr, gs));
-            HIPCHK(launch_radix_scatter(kin, vin, n, p * db, e->d_hist, nblocks, kout, vout,
-                                        p == passes - 1 ? e->d_posof : nullptr, gs));
+            if (p > 0) HIPCHK(launch_radix_hist(kin, n, p * db, B.d_hist, nblocks, gs));
+            HIPCHK(launch_scan(B.d_hist, B.d_hist, (uint64_t)nblocks << db, B.d_part, nullptr, gs));
+            HIPCHK(launch_radix_scatter(kin, vin, n, p * db, B.d_hist, nblocks, kout, vout,
+                                        p == passes - 1 ? B.d_posof : nullptr, gs));
             std::swap(kin, kout);
             std::swap(vin, vout);
         }
-        HIPCHK(launch_seg(kin, n, e->d_flag, e->d_pos, e->d_segs, gs, launch_scan, e->d_part, e->d_bsmall + 1));
-        HIPCHK(launch_gather(e->d_rec_o, vin, kin, n, e->d_posof, e->d_recs, e->d_prev, e->d_bsmall + 3, e->d_link,
-                             e->d_bst, e->epoch, e->d_bsmall + 0, gs));
+        HIPCHK(launch_seg(kin, n, B.d_flag, B.d_pos, B.d_segs, gs, B.d_part, sw + BS_NSEG));
+        HIPCHK(launch_gather(B.d_rec_o, vin, kin, n, B.d_posof, B.d_recs, B.d_prev, sw + BS_NPREV, B.d_link,
+                             B.d_bst, e->epoch, sw + BS_FLAGS, gs));
         if (int brc = bins(nullptr, nullptr, nullptr)) return brc;
     } else {
-        // ---- hot / cold group stage (kernels.hip k_grp_*): [77] hot_total (the cold region's start), [78] cold
-        // events, [80] hot segments, [81] (hot_total again), [82] cold segments, [76] the next batch's hot ids
+        // ---- hot / cold group stage (kernels.hip k_grp_*); its own words are BS_GRP .. BS_COLD_SEGS
         const uint32_t nhot = e->nhot;
         B.nhot = nhot;
-        uint32_t* words = e->d_flag;    // per event: W_HOT | W_ENT? | hot id << 12 | rank in its tile's run of the id;
+        uint32_t* words = B.d_flag;    // per event: W_HOT | W_ENT? | hot id << 12 | rank in its tile's run of the id;
                                         // cold: W_ENT? | sorted position (the last cold pass)
-        uint32_t* hot_off = e->d_pos;   // [tile][hot id] counts (tile-major, rows of nhot words), scanned in place: the
+        uint32_t* hot_off = B.d_pos;   // [tile][hot id] counts (tile-major, rows of nhot words), scanned in place: the
                                         // runs' sorted positions P (k_grp_records, k_post_w, k_hot_bmax read rows of it)
         uint32_t* ccnt = B.d_ccnt;      // per tile: cold events (compacted at the tile's start in k1 / v1)
-        HIPCHK(launch_grp_first(dev_ev, n, R, e->gbase, ring_mask, e->d_bsmall + 0, d_t0, e->d_prio, e->d_keyring,
+        HIPCHK(launch_grp_first(dev_ev, n, R, e->gbase, ring_mask, sw + BS_FLAGS, d_t0, e->d_prio, e->d_keyring,
                                 e->d_comp, dev_ext, dev_args, n_args, SG_MAX_CONTEXTS, dev_auth(e), dev_auth_ids(e),
                                 e->d_hot_tab, nhot, nblocks,
-                                words, hot_off, e->d_k1, e->d_v1, ccnt, e->d_hist, ublk, gs));
+                                words, hot_off, B.d_k1, B.d_v1, ccnt, B.d_hist, ublk, gs));
         if (int drc = decide_prev()) return drc;
-        HIPCHK(launch_hot_scan(hot_off, nblocks, nhot, e->d_hot_part, e->d_hot_hb, e->d_bsmall + 77, gs));
-        HIPCHK(launch_cold_n(n, e->d_bsmall + 77, e->d_bsmall + 78, gs));
+        HIPCHK(launch_hot_scan(hot_off, nblocks, nhot, e->d_hot_part, e->d_hot_hb, sw + BS_GRP, gs));
+        HIPCHK(launch_cold_n(n, sw + BS_GRP, sw + BS_COLD_N, gs));
         if (nblocks == 1) {  // one tile: the cold pairs sorted by one workgroup (k_cold_small), into k0 / v0
-            HIPCHK(launch_cold_small(kin, vin, ccnt, e->d_bsmall + 77, kout, vout, words, gs));
+            HIPCHK(launch_cold_small(kin, vin, ccnt, sw + BS_GRP, kout, vout, words, gs));
             std::swap(kin, kout);
             std::swap(vin, vout);
         }
         for (int p = 0; p < passes && nblocks > 1; ++p) {  // the cold (key, index) pairs
-            if (p > 0) HIPCHK(launch_radix_hist_n(kin, n, e->d_bsmall + 78, p * db, e->d_hist, nblocks, gs));
-            HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks << db, e->d_part, nullptr, gs));
+            if (p > 0) HIPCHK(launch_radix_hist_n(kin, n, sw + BS_COLD_N, p * db, B.d_hist, nblocks, gs));
+            HIPCHK(launch_scan(B.d_hist, B.d_hist, (uint64_t)nblocks << db, B.d_part, nullptr, gs));
             const bool last = p == passes - 1;
-            HIPCHK(launch_radix_scatter_x(kin, vin, n, p ? e->d_bsmall + 78 : nullptr, p ? nullptr : ccnt,
-                                          last ? e->d_bsmall + 77 : nullptr, p * db, e->d_hist, nblocks, kout, vout,
+            HIPCHK(launch_radix_scatter_x(kin, vin, n, p ? sw + BS_COLD_N : nullptr, p ? nullptr : ccnt,
+                                          last ? sw + BS_GRP : nullptr, p * db, B.d_hist, nblocks, kout, vout,
                                           last ? words : nullptr, gs));
             std::swap(kin, kout);
             std::swap(vin, vout);
         }
         // segments: the hot ids' (in id order), then the cold keys' [hot_total, n)
-        HIPCHK(launch_hot_segs(e->d_hot_hb, nhot, e->d_hot_list, e->d_segs, e->d_bsmall + 80, gs));
+        HIPCHK(launch_hot_segs(e->d_hot_hb, nhot, e->d_hot_list, B.d_segs, sw + BS_HOT_SEGS, gs));
         const uint64_t sc = nblocks + 64;
-        HIPCHK(launch_seg_cold(kin, n, e->d_bsmall + 77, e->d_bsmall + 80, ccnt + sc, ccnt + 2 * sc, e->d_segs, gs,
-                               launch_scan, e->d_part, e->d_bsmall + 82, e->d_bsmall + 1));
+        HIPCHK(launch_seg_cold(kin, n, sw + BS_GRP, sw + BS_HOT_SEGS, ccnt + sc, ccnt + 2 * sc, B.d_segs, gs,
+                               B.d_part, sw + BS_COLD_SEGS, sw + BS_NSEG));
         // the bins first: they read only the segments, the programs and the marks of k_grp_first, and say which
         // side tables the record kernels must build (SG_DEBUG_FLAGS & 32768: all of them, as the radix stage does)
         uint32_t *need_hot = nullptr, *need_blk = nullptr, *bmax = nullptr;
@@ -3060,24 +2856,19 @@ static int group_stage(sg_engine* e, int k, const sg_event* ev, const sg_event_e
         }
         if (int brc = bins(need_hot, need_blk, bmax)) return brc;
         HIPCHK(launch_grp_records(dev_ev, n, e->gbase, ring_mask, e->cfg.statistic_max_rt, words, hot_off, nhot, nblocks,
-                                  e->d_hot_hb, e->d_recs, vin, e->d_prev, e->d_bsmall + 3, e->d_bst,
-                                  e->d_bsmall + 0, dev_ext, dev_args, SG_MAX_CONTEXTS, e->d_link, e->epoch, need_hot,
+                                  e->d_hot_hb, B.d_recs, vin, B.d_prev, sw + BS_NPREV, B.d_bst,
+                                  sw + BS_FLAGS, dev_ext, dev_args, SG_MAX_CONTEXTS, B.d_link, e->epoch, need_hot,
                                   need_blk, R, dev_auth(e), dev_auth_ids(e), ublk, gs));
-        HIPCHK(launch_block_sums(e->d_recs, n, e->d_bst, e->d_link, e->epoch, e->d_bsmall + 0, kin, e->d_bsmall + 77,
+        HIPCHK(launch_block_sums(B.d_recs, n, B.d_bst, B.d_link, e->epoch, sw + BS_FLAGS, kin, sw + BS_GRP,
                                  need_blk, gs));
     }
     // the next batch's hot ids: this batch's resources of >= n / 8192 events (about one per 4096-event tile, so
     // that a tile's run of one hot id is more than a random write), at least 64
     const uint32_t hot_min = (uint32_t)std::max<uint64_t>(64, n / 8192);
     if (!B.radix)
-        HIPCHK(launch_hot_build(e->d_segs, e->d_bsmall + 1, mb, hot_min, R, e->d_hot_tab, e->d_hot_list, e->nhot,
-                                e->d_bsmall + 76, gs));
-    // [0] bflags [1] nseg [3] nprev [4..5] t0 [6..7] XF_MIX lists [8..8+N_BINS] bin offsets [72] wide XF_MIX events
-    // [73] hot ids marked for the side tables [74] PM_UBLK segments in cooperative bins (SEG_UBLK) [75] in lane bins
-    // [76] the next batch's hot ids [77..82] the hot / cold stage's own [83] events of XF_EMB segments [84] XF_EMB
-    // segments in cooperative bins [85] in lane bins
-    static_assert(8 + N_BINS + 1 <= 72 && HEAD_WORDS == 86, "head layout");
-    HIPCHK(hipMemcpyAsync(B.h_head, e->d_bsmall, HEAD_WORDS * 4, hipMemcpyDeviceToHost, gs));
+        HIPCHK(launch_hot_build(B.d_segs, sw + BS_NSEG, mb, hot_min, R, e->d_hot_tab, e->d_hot_list, e->nhot,
+                                sw + BS_HOT_NEXT, gs));
+    HIPCHK(hipMemcpyAsync(B.h_head, B.d_bsmall, BS_HEAD_WORDS * 4, hipMemcpyDeviceToHost, gs));
     HIPCHK(hipEventRecord(B.ev[1], gs));
     auto& G = B.g;
     G.n = n; G.n_args = n_args; G.gbase = e->gbase; G.ring_mask = ring_mask;
@@ -3101,26 +2892,19 @@ static int accept_grouped(sg_engine* e, bool drop = false) {
     e->grouped = -1;
     HIPCHK(hipEventSynchronize(B.ev[1]));
     const uint32_t* head = B.h_head;
-    if (!B.radix) e->nhot = std::min<uint32_t>(head[76], hot_max());
+    if (!B.radix) e->nhot = std::min<uint32_t>(head[BS_HOT_NEXT], hot_max());
     if (drop) return SG_OK;
-    B.hot_marked = head[73];
-    B.ublk_coop = head[74];
-    B.ublk_lane = head[75];
-    B.emb_ub = e->emb_n ? head[83] : 0u;
-    B.emb_coop = e->emb_n ? head[84] : 0u;
-    B.emb_lane = e->emb_n ? head[85] : 0u;
-    const uint32_t bflags = head[0];
-    if (bflags & BF_BAD_RES) return fail(SG_EINVAL, "event res_id >= max_resources");
-    if (bflags & BF_BAD_REF)
-        return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
-    if (bflags & BF_TSPAN) return fail(SG_EINVAL, "a batch must span less than 2^31 ms");
-    if (bflags & BF_BACKWARD) return fail(SG_EINVAL, "event timestamps must be non-decreasing (SURVEY Q3)");
-    if (bflags & BF_BAD_ARGS)
-        return fail(SG_EINVAL, "an sg_event_ext names args outside the table (or more than SG_MAX_ARGS, or a bad kind)");
+    B.hot_marked = head[BS_HOT_MARKED];
+    B.ublk_coop = head[BS_UBLK];
+    B.ublk_lane = head[BS_UBLK_LANE];
+    B.emb_ub = e->emb_n ? head[BS_EMB] : 0u;
+    B.emb_coop = e->emb_n ? head[BS_EMB_COOP] : 0u;
+    B.emb_lane = e->emb_n ? head[BS_EMB_LANE] : 0u;
+    if (int vrc = group_verdict(head[BS_FLAGS])) return vrc;
     // the decide stage's only allocation (the value-parallel passes' scratch) before the batch is counted: past
     // this point nothing but a device error can keep its decide stage from being enqueued
-    if (e->has_mix && head[7] && (e->pv_on || e->pvt_on) && head[72]) {
-        if (int prc = ensure_pv(e, head[72], head[7])) return prc;
+    if (e->has_mix && head[BS_MIX_NW] && (e->pv_on || e->pvt_on) && head[BS_MIX_WIDE]) {
+        if (int prc = ensure_pv(e, head[BS_MIX_WIDE], head[BS_MIX_NW])) return prc;
     }
     e->inflight.push_back({B.g.set, B.hot_marked, B.ublk_coop, B.ublk_lane, B.emb_coop, B.emb_lane});
     ++e->seq;
@@ -3158,8 +2942,8 @@ static int decide_stage(sg_engine* e, int k) {
 // The decide stage proper (reference resolution, chain grants, decide kernels, post), enqueued on the decide streams
 // behind the previous batch's.
 static int decide_enqueue(sg_engine* e, int k) {
-    activate(e, k);
     auto& B = e->slot[k];
+    uint32_t* const sw = B.d_bsmall;  // the batch's small words (BS_*)
     const auto& G = B.g;
     hipStream_t st = e->stream;
     const uint64_t n = G.n, n_args = G.n_args, ring_mask = G.ring_mask;
@@ -3171,67 +2955,25 @@ static int decide_enqueue(sg_engine* e, int k) {
     const bool ext = G.ext, host_out = G.host_out, force_lane = G.force_lane;
     (void)n_args;
     const uint32_t* head = B.h_head;  // (the slot's next group stage, which refills it, is enqueued after this returns)
-    const uint32_t m = head[1];
-    const uint32_t nprev = head[3];
+    const uint32_t m = head[BS_NSEG];
+    const uint32_t nprev = head[BS_NPREV];
     int64_t t0 = 0;
-    std::memcpy(&t0, head + 4, 8);
-    const uint32_t bflags = head[0];
-    const uint32_t* off = head + 8;
+    std::memcpy(&t0, head + BS_T0, 8);
+    const uint32_t bflags = head[BS_FLAGS];
+    const uint32_t* off = head + BS_BIN_OFF;
     uint32_t bin_n[N_BINS];
     for (int b = 0; b < N_BINS; ++b) bin_n[b] = off[b + 1] - off[b];
     // ---- 3. decide: cooperative bins on their own streams, lane bins on the main stream (state for every kernel)
     DevCfg dc;
-    std::memset(&dc, 0, sizeof(dc));
-    dc.max_rt = e->cfg.statistic_max_rt;
-    dc.occupy_timeout = e->cfg.occupy_timeout_ms;
-    dc.max_chain = e->cfg.max_slot_chain_size;
-    dc.switch_on = e->cfg.switch_on;
-    dc.ring_mask = ring_mask;
-    dc.snap_hi = e->snap_hi;
-    dc.dbg_flags = e->dbg_flags;
-    dc.heads = e->has_head ? 1u : 0u;
-    DevState S{};
-    std::memset(&S, 0, sizeof(S));
-    S.sec = e->d_sec;
-    S.minb = e->d_minb;
-    S.info = e->d_info;
-    S.prog = e->d_prog;
-    S.rules = e->d_rules;
-    S.rstate = e->d_rstate;
-    S.hot = e->d_hot;
-    S.pmap = e->d_pmap;
-    S.pbkt = e->d_pbkt;
-    S.pdat = e->d_pdat;
-    S.pbm = e->d_pbm;
-    S.ppre = e->d_ppre;
-    S.tmid = e->d_tmid;
-    S.ring = e->d_ring;
-    S.sink = e->d_sink;
-    S.borrow = e->d_borrow;
-    S.prio = e->d_prio;
-    S.key_ring = e->d_keyring;
+    DevState S;
+    fill_state(e, B, ring_mask, dev_ext, dev_args, dc, S);
     S.gbase = G.gbase;
-    S.link = e->d_link;
-    S.bst = e->d_bst;
-    S.pend = e->d_pend;
-    S.spans = e->d_spans;
-    S.nspan = e->d_bsmall + 120;
-    S.span_cap = e->span_cap;
     S.epoch = G.epoch;
     S.skip_ok = !(bflags & (BF_MULTI_LINK | BF_ZERO_CNT)) && !(e->dbg_flags & 4) ? 1u : 0u;
     S.skip_min = skip_min;  // (the bins marked the side tables by it)
-    S.ext = dev_ext;
-    S.args = dev_args;
-    S.aux_tab = e->d_auxtab;
-    S.aux_count = e->d_auxcnt;
-    S.aux_cap = e->cfg.aux_node_capacity;
-    S.aux_mask = e->aux_mask;
-    S.max_ctx = SG_MAX_CONTEXTS;
-    S.auth = dev_auth(e);
-    S.auth_ids = dev_auth_ids(e);
     // ---- decide stage, in order after the previous batch's: references into earlier batches first
     HIPCHK(hipStreamWaitEvent(st, B.ev[1], 0));
-    const uint32_t n_mix = e->has_mix ? head[6] : 0u, n_mixw = e->has_mix ? head[7] : 0u;
+    const uint32_t n_mix = e->has_mix ? head[BS_MIX_N] : 0u, n_mixw = e->has_mix ? head[BS_MIX_NW] : 0u;
     // SG_DEBUG_FLAGS & 8 (diagnostics): every decide kernel on the main stream, one after the other
     const bool serial_bins = (e->dbg_flags & 8) != 0;
     const bool pre_split = (n_mix || n_mixw) && !serial_bins;
@@ -3240,32 +2982,31 @@ static int decide_enqueue(sg_engine* e, int k) {
     // so with every chain granted (k_pv_prep then knows the grants' outcome) they start as soon as this batch is
     // grouped, on bin_stream[1] beside the previous batch's post pass (their own scratch, pvb; the post pass has pvbt)
     const uint32_t grant_all = (e->cfg.switch_on && e->cfg.max_slot_chain_size <= 0) ? 1u : 0u;
-    if (n_mixw && (e->pv_on || e->pvt_on) && head[72]) {
-        if (int prc = ensure_pv(e, head[72], n_mixw)) return prc;
+    if (n_mixw && (e->pv_on || e->pvt_on) && head[BS_MIX_WIDE]) {
+        if (int prc = ensure_pv(e, head[BS_MIX_WIDE], n_mixw)) return prc;
         e->pv_last_m = n_mixw;
     }
-    const bool pv_ran = n_mixw && e->pv_on && head[72];
+    const bool pv_ran = n_mixw && e->pv_on && head[BS_MIX_WIDE];
     const bool pv_early = pv_ran && pre_split && grant_all && !e->has_multi;
     if (pv_early) {
         HIPCHK(hipStreamWaitEvent(ps, B.ev[1], 0));
-        HIPCHK(launch_pv_a(e->d_recs, vin, e->d_segs, B.d_mix + B.mix_cap, n_mixw, S, dc, e->d_dec, e->d_pvseg, e->pvb,
-                           head[72], e->d_pvtot, e->d_pvhist, e->d_pvpart, ps, launch_radix_hist_n,
-                           launch_radix_scatter_n, launch_scan, radix_tile(), e->d_pvrest, grant_all));
+        HIPCHK(launch_pv_a(B.d_recs, vin, B.d_segs, B.d_mix + B.mix_cap, n_mixw, S, dc, B.d_dec, e->d_pvseg, e->pvb,
+                           head[BS_MIX_WIDE], e->d_pvtot, e->d_pvhist, e->d_pvpart, ps, radix_tile(), e->d_pvrest, grant_all));
     }
-    HIPCHK(launch_resolve(e->d_prev, nprev, e->d_ring, e->d_recs, vin, dev_ext, st));
+    HIPCHK(launch_resolve(B.d_prev, nprev, e->d_ring, B.d_recs, vin, dev_ext, st));
     // ---- chain cap (CtSph.lookProcessChain): grant chains in order of first ENTRY.  First on the decide stream: the
     // pre pass's eligibility reads the chain flags (it ran beside the grants and raced them)
     if (e->cfg.switch_on && (e->cfg.max_slot_chain_size <= 0 || e->n_chains < (uint32_t)e->cfg.max_slot_chain_size)) {
         const bool grant_all = e->cfg.max_slot_chain_size <= 0;
-        HIPCHK(launch_chain(e->d_recs, vin, e->d_segs, m, e->d_info, grant_all ? 1 : 0, e->d_bsmall + 2, e->d_cand,
+        HIPCHK(launch_chain(B.d_recs, vin, B.d_segs, m, e->d_info, grant_all ? 1 : 0, sw + BS_NCAND, B.d_cand,
                             dev_ev, e->d_prog, dev_ext, SG_MAX_CONTEXTS, st));
         if (!grant_all) {
             uint32_t ncand = 0;
-            HIPCHK(hipMemcpyAsync(&ncand, e->d_bsmall + 2, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&ncand, sw + BS_NCAND, 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             if (ncand) {
                 std::vector<uint64_t> cand(ncand);
-                HIPCHK(hipMemcpy(cand.data(), e->d_cand, ncand * 8ull, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(cand.data(), B.d_cand, ncand * 8ull, hipMemcpyDeviceToHost));
                 std::sort(cand.begin(), cand.end());  // by batch index of the first ENTRY
                 std::vector<uint64_t> upd;
                 std::unordered_map<uint32_t, int> seen;  // RELATE components list every ENTRY
@@ -3277,8 +3018,8 @@ static int decide_enqueue(sg_engine* e, int k) {
                     upd.push_back(((uint64_t)(grant ? NI_CHAIN : NI_REJECTED) << 32) | res | (1ull << 63));
                 }
                 ncand = (uint32_t)upd.size();
-                HIPCHK(hipMemcpyAsync(e->d_cand, upd.data(), ncand * 8ull, hipMemcpyHostToDevice, st));
-                HIPCHK(launch_set_flags(e->d_info, e->d_cand, ncand, st));
+                HIPCHK(hipMemcpyAsync(B.d_cand, upd.data(), ncand * 8ull, hipMemcpyHostToDevice, st));
+                HIPCHK(launch_set_flags(e->d_info, B.d_cand, ncand, st));
                 HIPCHK(hipStreamSynchronize(st));
             }
         }
@@ -3299,9 +3040,8 @@ static int decide_enqueue(sg_engine* e, int k) {
         HIPCHK(hipStreamWaitEvent(ps, e->fork0, 0));
     }
     if (pv_ran && !pv_early)
-        HIPCHK(launch_pv_a(e->d_recs, vin, e->d_segs, B.d_mix + B.mix_cap, n_mixw, S, dc, e->d_dec, e->d_pvseg, e->pvb,
-                           head[72], e->d_pvtot, e->d_pvhist, e->d_pvpart, ps, launch_radix_hist_n,
-                           launch_radix_scatter_n, launch_scan, radix_tile(), e->d_pvrest, grant_all));
+        HIPCHK(launch_pv_a(B.d_recs, vin, B.d_segs, B.d_mix + B.mix_cap, n_mixw, S, dc, B.d_dec, e->d_pvseg, e->pvb,
+                           head[BS_MIX_WIDE], e->d_pvtot, e->d_pvhist, e->d_pvpart, ps, radix_tile(), e->d_pvrest, grant_all));
     // param map regions grown for this batch's segments before anything touches a map; the pool's use, for the
     // compaction check of a later submit
     if (e->pool_nb) {
@@ -3310,10 +3050,10 @@ static int decide_enqueue(sg_engine* e, int k) {
         Sg.prog = e->d_prog; Sg.rules = e->d_rules; Sg.tmid = e->d_tmid; Sg.prio = e->d_prio;
         Sg.pmap = e->d_pmap; Sg.pbkt = e->d_pbkt; Sg.pdat = e->d_pdat; Sg.pbm = e->d_pbm;
         const uint32_t nm = (uint32_t)e->pmap_key.size();
-        HIPCHK(launch_pm_grow(e->d_segs, e->d_bsmall + 1, mb, Sg, e->d_pool_next, e->pool_nb, e->d_bsmall + 0, e->d_pmoves,
+        HIPCHK(launch_pm_grow(B.d_segs, sw + BS_NSEG, mb, Sg, e->d_pool_next, e->pool_nb, sw + BS_FLAGS, e->d_pmoves,
                               e->d_pmoves ? reinterpret_cast<uint32_t*>(e->d_pmoves + e->pmoves_cap) : nullptr,
                               (uint32_t)e->pmoves_cap, G.epoch, nm, e->d_pbkt2, e->d_pdat2, e->d_pcwork,
-                              e->d_pcwork + e->pmoves_cap, e->d_pcwork + 2 * e->pmoves_cap, launch_scan, st));
+                              e->d_pcwork + e->pmoves_cap, e->d_pcwork + 2 * e->pmoves_cap, st));
         HIPCHK(hipMemcpyAsync(e->h_pool_next, e->d_pool_next, PC_WORDS * 8, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipEventRecord(B.ev[2], st));
@@ -3322,34 +3062,34 @@ static int decide_enqueue(sg_engine* e, int k) {
         HIPCHK(hipStreamWaitEvent(ps, e->grown, 0));
     }
     if (pv_ran) {  // the rest of the value-parallel pre pass
-        HIPCHK(launch_pv_b(e->d_recs, e->d_segs, B.d_mix + B.mix_cap, n_mixw, S, t0, e->d_dec, e->d_bsmall + 0,
-                           e->d_pvseg, e->pvb, head[72], e->d_pvtot, e->d_pvpart, (bflags & BF_ZERO_CNT) ? 0u : 1u, ps,
-                           launch_scan, e->d_pvrest));
+        HIPCHK(launch_pv_b(B.d_recs, B.d_segs, B.d_mix + B.mix_cap, n_mixw, S, t0, B.d_dec, sw + BS_FLAGS,
+                           e->d_pvseg, e->pvb, head[BS_MIX_WIDE], e->d_pvtot, e->d_pvpart, (bflags & BF_ZERO_CNT) ? 0u : 1u, ps,
+                           e->d_pvrest));
     }
     if (n_mix || n_mixw)
-        HIPCHK(launch_pq_mix(0, e->d_recs, dev_ev, vin, e->d_segs, B.d_mix, n_mix, B.mix_cap, n_mixw, S, dc, t0,
-                             e->d_dec, e->d_bsmall + 0, ps, pv_ran ? e->d_pvrest + 1 : nullptr, e->d_pvrest));
+        HIPCHK(launch_pq_mix(0, B.d_recs, dev_ev, vin, B.d_segs, B.d_mix, n_mix, B.mix_cap, n_mixw, S, dc, t0,
+                             B.d_dec, sw + BS_FLAGS, ps, pv_ran ? e->d_pvrest + 1 : nullptr, e->d_pvrest));
     // Pre-blocked ENTRYs of the cooperative bins' segments (SEG_UBLK): their words and RF_PBLK after the param pre
     // pass (whose block comes first) and before every owner; launched only in a batch that has such a segment
     // (and the ENTRYs the embedded token call answered BLOCKED, in a batch that made requests)
-    if (head[74] || (S.emb && B.emb_coop))
-        HIPCHK(launch_ublk_words(e->d_recs, e->d_segs, e->d_order + off[BIN_J16], off[BIN_J8 + 1] - off[BIN_J16], e->d_dec,
-                                 e->d_bsmall + 119, S.emb, e->d_bsmall + 108, ps));
+    if (head[BS_UBLK] || (S.emb && B.emb_coop))
+        HIPCHK(launch_ublk_words(B.d_recs, B.d_segs, B.d_order + off[BIN_J16], off[BIN_J8 + 1] - off[BIN_J16], B.d_dec,
+                                 sw + BS_UBLK_WORDS, S.emb, sw + BS_EMB_AHEAD, ps));
     HIPCHK(hipEventRecord(e->fork, ps));
     auto lane_bins = [&]() -> int {
         {
             DevState Sl = S;
             Sl.dbg = e->d_dbg;  // SG_KPROF builds: lane-kernel phase cycles in dbg[32..36]
-            HIPCHK(launch_decide_bin(BIN_LANE, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[BIN_LANE],
-                                     off[BIN_LANE + LANE_BINS] - off[BIN_LANE], Sl, dc, t0, e->d_dec, e->d_bsmall + 0, st));
+            HIPCHK(launch_decide_bin(BIN_LANE, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[BIN_LANE],
+                                     off[BIN_LANE + LANE_BINS] - off[BIN_LANE], Sl, dc, t0, B.d_dec, sw + BS_FLAGS, st));
         }
-        HIPCHK(launch_decide_bin(BIN_LANE16, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[BIN_LANE16],
-                                 off[BIN_LANE16 + LANE_BINS] - off[BIN_LANE16], S, dc, t0, e->d_dec, e->d_bsmall + 0, st));
+        HIPCHK(launch_decide_bin(BIN_LANE16, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[BIN_LANE16],
+                                 off[BIN_LANE16 + LANE_BINS] - off[BIN_LANE16], S, dc, t0, B.d_dec, sw + BS_FLAGS, st));
         {
             DevState Sl = S;
             Sl.dbg = e->d_dbg;  // SG_KPROF builds: lane-kernel phase cycles in dbg[32..37]
-            HIPCHK(launch_decide_bin(BIN_LITE, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[BIN_LITE],
-                                     off[BIN_LITE + LANE_BINS] - off[BIN_LITE], Sl, dc, t0, e->d_dec, e->d_bsmall + 0, st));
+            HIPCHK(launch_decide_bin(BIN_LITE, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[BIN_LITE],
+                                     off[BIN_LITE + LANE_BINS] - off[BIN_LITE], Sl, dc, t0, B.d_dec, sw + BS_FLAGS, st));
         }
         return SG_OK;
     };
@@ -3370,8 +3110,8 @@ static int decide_enqueue(sg_engine* e, int k) {
             Sb.dbg = (e->prof_bin == 0 && e->d_dbg) ? e->d_dbg : nullptr;
             hipStream_t bs = (serial_bins || !j8_own) ? st : e->bin_stream[0];
             if (bs != st) HIPCHK(hipStreamWaitEvent(bs, e->fork, 0));
-            HIPCHK(launch_decide_bin(BIN_J8, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[BIN_J8], bin_n[BIN_J8], Sb, dc,
-                                     t0, e->d_dec, e->d_bsmall + 0, bs));
+            HIPCHK(launch_decide_bin(BIN_J8, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[BIN_J8], bin_n[BIN_J8], Sb, dc,
+                                     t0, B.d_dec, sw + BS_FLAGS, bs));
             if (bs != st) HIPCHK(hipEventRecord(e->join[0], bs));
         }
         if (!bin_n[b]) continue;
@@ -3379,8 +3119,8 @@ static int decide_enqueue(sg_engine* e, int k) {
         Sb.dbg = (c == e->prof_bin && e->d_dbg) ? e->d_dbg : nullptr;
         hipStream_t bs = serial_bins ? st : e->bin_stream[c];
         if (!serial_bins) HIPCHK(hipStreamWaitEvent(bs, e->fork, 0));
-        HIPCHK(launch_decide_bin(b, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[b], bin_n[b], Sb, dc, t0,
-                                 e->d_dec, e->d_bsmall + 0, bs));
+        HIPCHK(launch_decide_bin(b, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[b], bin_n[b], Sb, dc, t0,
+                                 B.d_dec, sw + BS_FLAGS, bs));
         HIPCHK(hipEventRecord(e->join[c], bs));
     }
     // hot-parameter owners (k_pq): the wide ones beside J16, the narrow ones beside J4
@@ -3391,8 +3131,8 @@ static int decide_enqueue(sg_engine* e, int k) {
         if (!serial_bins && !bin_n[coop[c]] && !(c == 0 && j8_own)) HIPCHK(hipStreamWaitEvent(bs, e->fork, 0));
         DevState Sp = S;
         Sp.dbg = (c == 0 && e->prof_bin == 3) ? e->d_dbg : nullptr;  // SG_PROF_BIN=3: k_pq<16> phase cycles (kprof builds)
-        HIPCHK(launch_pq(c == 0, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[b], bin_n[b], Sp, dc, t0, e->d_dec,
-                         e->d_bsmall + 0, bs));
+        HIPCHK(launch_pq(c == 0, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[b], bin_n[b], Sp, dc, t0, B.d_dec,
+                         sw + BS_FLAGS, bs));
         HIPCHK(hipEventRecord(e->join[c], bs));
     }
     if (!pre_split)
@@ -3404,7 +3144,7 @@ static int decide_enqueue(sg_engine* e, int k) {
     const bool aux_early = ext && !bin_n[BIN_PQ4] && !serial_bins && (force_lane || lane_max >= 256u) &&
                            (!bin_n[BIN_PQ16] || e->pq_wide >= 256u);
     if (aux_early)
-        HIPCHK(launch_aux_cold(e->d_recs, e->d_segs, e->d_bsmall + 130, B.d_ashort, S, dc, t0, e->d_dec, e->d_bsmall + 0, st));
+        HIPCHK(launch_aux_cold(B.d_recs, B.d_segs, sw + BS_AUX, B.d_ashort, S, dc, t0, B.d_dec, sw + BS_FLAGS, st));
     // J1: after the lane bins on the main stream, or (SG_J1_STREAM=1, and with the short aux nodes on the main stream)
     // after J16 / J8 on bin_stream[0]
     const bool j1_b0 = bin_n[BIN_J1] && !serial_bins && (e->j1_stream == 1 || (e->j1_stream < 0 && aux_early));
@@ -3419,8 +3159,8 @@ static int decide_enqueue(sg_engine* e, int k) {
             hipStream_t bs = e->bin_stream[c];
             const bool ran = c == 0 ? (bin_n[BIN_J16] || bin_n[BIN_J8] || bin_n[BIN_PQ16]) : (bin_n[BIN_J4] || bin_n[BIN_PQ4]);
             if (!ran) HIPCHK(hipStreamWaitEvent(bs, e->fork, 0));
-            HIPCHK(launch_decide_bin(BIN_J1, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[BIN_J1] + (c ? h : 0),
-                                     c ? bin_n[BIN_J1] - h : h, Sj, dc, t0, e->d_dec, e->d_bsmall + 0, bs));
+            HIPCHK(launch_decide_bin(BIN_J1, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[BIN_J1] + (c ? h : 0),
+                                     c ? bin_n[BIN_J1] - h : h, Sj, dc, t0, B.d_dec, sw + BS_FLAGS, bs));
             HIPCHK(hipEventRecord(e->join[c], bs));
         }
     } else if (bin_n[BIN_J1]) {
@@ -3428,8 +3168,8 @@ static int decide_enqueue(sg_engine* e, int k) {
         Sj.dbg = (e->prof_bin == 2 && e->d_dbg) ? e->d_dbg : nullptr;
         hipStream_t bs = j1_b0 ? e->bin_stream[0] : st;
         if (j1_b0 && !(bin_n[BIN_J16] || bin_n[BIN_J8] || bin_n[BIN_PQ16])) HIPCHK(hipStreamWaitEvent(bs, e->fork, 0));
-        HIPCHK(launch_decide_bin(BIN_J1, e->d_recs, dev_ev, vin, e->d_segs, e->d_order + off[BIN_J1], bin_n[BIN_J1], Sj, dc,
-                                 t0, e->d_dec, e->d_bsmall + 0, bs));
+        HIPCHK(launch_decide_bin(BIN_J1, B.d_recs, dev_ev, vin, B.d_segs, B.d_order + off[BIN_J1], bin_n[BIN_J1], Sj, dc,
+                                 t0, B.d_dec, sw + BS_FLAGS, bs));
         if (j1_b0) HIPCHK(hipEventRecord(e->join[0], bs));
     }
     for (int c = 0; c < 2; ++c)
@@ -3437,34 +3177,33 @@ static int decide_enqueue(sg_engine* e, int k) {
             HIPCHK(hipStreamWaitEvent(st, e->join[c], 0));
     // verdicts of the frozen spans the cooperative kernels skipped
     if (S.skip_ok && (bin_n[BIN_J16] || bin_n[BIN_J8] || bin_n[BIN_J4]))
-        HIPCHK(launch_fill(e->d_spans, S.nspan, e->span_cap, e->d_recs, e->d_prog, e->d_rules, e->d_dec, st));
+        HIPCHK(launch_fill(B.d_spans, S.nspan, e->span_cap, B.d_recs, e->d_prog, e->d_rules, B.d_dec, st));
     // XF_MIX: the thread-count maps and ParameterMetric bits from the final verdicts (the long ones value-parallel
     // where the maps do not overflow, pvalue.hip; the rest by k_pq's post pass)
-    if (n_mixw && e->pvt_on && head[72])
-        HIPCHK(launch_pvt(e->d_recs, dev_ev, vin, e->d_segs, B.d_mix + B.mix_cap, n_mixw, S, dc, e->d_dec,
-                          e->d_bsmall + 0, e->d_pvtseg, e->pvbt, head[72], e->d_pvtot + 4, e->d_pvthist, e->d_pvtpart, st,
-                          launch_radix_hist_n, launch_radix_scatter_n, launch_scan, radix_tile(),
-                          e->d_pvrest + e->pvseg_cap + 1));
-    const bool pvt_ran = n_mixw && e->pvt_on && head[72];
+    if (n_mixw && e->pvt_on && head[BS_MIX_WIDE])
+        HIPCHK(launch_pvt(B.d_recs, dev_ev, vin, B.d_segs, B.d_mix + B.mix_cap, n_mixw, S, dc, B.d_dec,
+                          sw + BS_FLAGS, e->d_pvtseg, e->pvbt, head[BS_MIX_WIDE], e->d_pvtot + 4, e->d_pvthist, e->d_pvtpart, st,
+                          radix_tile(), e->d_pvrest + e->pvseg_cap + 1));
+    const bool pvt_ran = n_mixw && e->pvt_on && head[BS_MIX_WIDE];
     uint32_t* prest = e->d_pvrest + e->pvseg_cap + 1;
     if (n_mix || n_mixw)
-        HIPCHK(launch_pq_mix(1, e->d_recs, dev_ev, vin, e->d_segs, B.d_mix, n_mix, B.mix_cap, n_mixw, S, dc, t0,
-                             e->d_dec, e->d_bsmall + 0, st, pvt_ran ? prest + 1 : nullptr, prest));
+        HIPCHK(launch_pq_mix(1, B.d_recs, dev_ev, vin, B.d_segs, B.d_mix, n_mix, B.mix_cap, n_mixw, S, dc, t0,
+                             B.d_dec, sw + BS_FLAGS, st, pvt_ran ? prest + 1 : nullptr, prest));
     // origin / context nodes of the segments decided off k_lane<16>, from the committed verdicts (aux.hip)
     if (ext)
-        HIPCHK(launch_aux(e->d_recs, e->d_segs, e->d_bsmall + 130, aux_early ? nullptr : B.d_ashort, B.d_along, B.d_apiece,
-                          B.d_amulti, S, dc, t0, e->d_dec, e->d_auxpool, e->auxpool_cap, e->d_bsmall + 134, e->d_auxmeta,
-                          e->d_bsmall + 0, st));
+        HIPCHK(launch_aux(B.d_recs, B.d_segs, sw + BS_AUX, aux_early ? nullptr : B.d_ashort, B.d_along, B.d_apiece,
+                          B.d_amulti, S, dc, t0, B.d_dec, e->d_auxpool, e->auxpool_cap, sw + BS_AUX_POOL_N, e->d_auxmeta,
+                          sw + BS_FLAGS, st));
     // the global inbound node from the same verdicts (inbound.hip), when it is tracked
     if (e->inb_on)
-        HIPCHK(launch_inbound(e->d_recs, e->d_dec, n, dev_ev, vin, S, dc, t0, e->d_inbpart, e->d_inb, st));
+        HIPCHK(launch_inbound(B.d_recs, B.d_dec, n, dev_ev, vin, S, dc, t0, e->d_inbpart, e->d_inb, st));
     HIPCHK(hipEventRecord(B.ev[3], st));
     // ---- 4. decisions back to submission order + status ring
-    if (B.radix) HIPCHK(launch_post(e->d_posof, e->d_dec, n, G.gbase, e->d_ring, ring_mask, dev_out, st));
-    else HIPCHK(launch_post_w(e->d_flag, e->d_pos, B.nhot, e->d_dec, n, G.gbase, e->d_ring, ring_mask, dev_out, st));
+    if (B.radix) HIPCHK(launch_post(B.d_posof, B.d_dec, n, G.gbase, e->d_ring, ring_mask, dev_out, st));
+    else HIPCHK(launch_post_w(B.d_flag, B.d_pos, B.nhot, B.d_dec, n, G.gbase, e->d_ring, ring_mask, dev_out, st));
     if (host_out) HIPCHK(hipMemcpyAsync(out, dev_out, n * 4, hipMemcpyDeviceToHost, st));
     // the flags and the span count for collect(), before the slot's next group stage clears them
-    HIPCHK(hipMemcpyAsync(e->h_mirror + (size_t)G.set * MIRROR_WORDS, e->d_bsmall, MIRROR_WORDS * 4, hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(e->h_mirror + (size_t)G.set * BS_MIRROR_WORDS, B.d_bsmall, BS_MIRROR_WORDS * 4, hipMemcpyDeviceToHost,
                           st));
     HIPCHK(hipEventRecord(B.ev[4], st));
     B.last_post = B.ev[4];
@@ -3566,103 +3305,53 @@ static int tiny_impl(sg_engine* e, const sg_event* ev, const sg_event_ext* ext, 
     if ((rc = ensure_pool2(e))) return rc;
     const unsigned long long pfloor = e->h_pool_next ? e->h_pool_next[PC_FLOOR] : 0;
     if (e->pool_nb && e->h_pool_next[PC_NEXT] > pfloor + (e->pool_nb - pfloor) / 2) return TINY_FALLBACK;  // compaction due
-    const int k = e->cur;
-    activate(e, k);
-    auto& B = e->slot[k];
+    auto& B = e->slot[e->cur];
     hipStream_t st = e->stream;
     const sg_event* dev_ev = ev;
     const bool host_out = !is_device_ptr(out);
     if (!is_device_ptr(ev)) {
-        HIPCHK(hipMemcpyAsync(e->d_ev, ev, n * sizeof(sg_event), hipMemcpyHostToDevice, st));
-        dev_ev = e->d_ev;
+        HIPCHK(hipMemcpyAsync(B.d_ev, ev, n * sizeof(sg_event), hipMemcpyHostToDevice, st));
+        dev_ev = B.d_ev;
     }
-    uint32_t* dev_out = host_out ? e->d_out : out;
-    const sg_event_ext* dev_ext = ext;
-    const sg_arg* dev_args = n_args ? args : nullptr;
-    if (ext && !is_device_ptr(ext)) {
-        if (n > B.ext_cap) {
-            dfree(B.d_ext);
-            B.ext_cap = std::max<uint64_t>(n, 1u << 16);
-            HIPCHK(hipMalloc(&B.d_ext, B.ext_cap * sizeof(sg_event_ext)));
-        }
-        HIPCHK(hipMemcpyAsync(B.d_ext, ext, n * sizeof(sg_event_ext), hipMemcpyHostToDevice, st));
-        dev_ext = B.d_ext;
-    }
-    if (n_args && !is_device_ptr(args)) {
-        if (n_args > B.args_cap) {
-            dfree(B.d_args);
-            B.args_cap = std::max<uint64_t>(n_args, 1u << 16);
-            HIPCHK(hipMalloc(&B.d_args, B.args_cap * sizeof(sg_arg)));
-        }
-        HIPCHK(hipMemcpyAsync(B.d_args, args, n_args * sizeof(sg_arg), hipMemcpyHostToDevice, st));
-        dev_args = B.d_args;
-    }
+    uint32_t* dev_out = host_out ? B.d_out : out;
+    const sg_event_ext* dev_ext;
+    const sg_arg* dev_args;
+    if ((rc = stage_ext_args(B, ext, n, args, n_args, st, &dev_ext, &dev_args))) return rc;
     if (++e->epoch == 0) e->epoch = 1;
     DevCfg dc;
-    std::memset(&dc, 0, sizeof(dc));
-    dc.max_rt = e->cfg.statistic_max_rt;
-    dc.occupy_timeout = e->cfg.occupy_timeout_ms;
-    dc.max_chain = e->cfg.max_slot_chain_size;
-    dc.switch_on = e->cfg.switch_on;
-    dc.ring_mask = (1ull << e->cfg.status_ring_log2) - 1;
-    dc.snap_hi = e->snap_hi;
-    dc.dbg_flags = e->dbg_flags;
-    dc.heads = e->has_head ? 1u : 0u;
-    DevState S{};
-    std::memset(&S, 0, sizeof(S));
-    S.sec = e->d_sec; S.minb = e->d_minb; S.info = e->d_info; S.prog = e->d_prog; S.rules = e->d_rules;
-    S.rstate = e->d_rstate; S.hot = e->d_hot; S.pmap = e->d_pmap; S.pbkt = e->d_pbkt; S.pdat = e->d_pdat;
-    S.pbm = e->d_pbm; S.ppre = e->d_ppre; S.tmid = e->d_tmid; S.ring = e->d_ring; S.sink = e->d_sink;
-    S.borrow = e->d_borrow; S.prio = e->d_prio; S.key_ring = e->d_keyring; S.gbase = e->gbase; S.link = e->d_link;
-    S.bst = e->d_bst; S.pend = e->d_pend; S.spans = e->d_spans; S.nspan = e->d_bsmall + 120; S.span_cap = e->span_cap;
-    S.epoch = e->epoch; S.skip_ok = 0; S.skip_min = e->skip_min; S.ext = dev_ext; S.args = dev_args;
-    S.aux_tab = e->d_auxtab; S.aux_count = e->d_auxcnt; S.aux_cap = e->cfg.aux_node_capacity; S.aux_mask = e->aux_mask;
-    S.max_ctx = SG_MAX_CONTEXTS;
-    S.auth = dev_auth(e);
-    S.auth_ids = dev_auth_ids(e);
+    DevState S;
+    fill_state(e, B, (1ull << e->cfg.status_ring_log2) - 1, dev_ext, dev_args, dc, S);
+    S.gbase = e->gbase;
+    S.epoch = e->epoch;
+    S.skip_ok = 0;
+    S.skip_min = e->skip_min;
     // the chain grants: every one in place (no cap), none (a cap reached: CtSph.lookProcessChain then returns null),
     // or the host's, in first-ENTRY order (the batched path)
     const int cap = e->cfg.max_slot_chain_size;
     const uint32_t grants = cap <= 0 ? 1u : e->n_chains >= (uint32_t)cap ? 2u : 0u;
     HIPCHK(launch_tiny(dev_ev, (uint32_t)n, S, dc, e->cfg.max_resources, e->d_prio, e->d_comp, n_args, grants,
-                       e->d_pool_next, e->pool_nb, e->epoch, e->d_recs, e->d_v0, e->d_dec, e->d_segs, e->d_bsmall,
+                       e->d_pool_next, e->pool_nb, e->epoch, B.d_recs, B.d_v0, B.d_dec, B.d_segs, B.d_bsmall + BS_FLAGS,
                        dev_out, st));
     uint32_t bflags = 0;
-    HIPCHK(hipMemcpyAsync(&bflags, e->d_bsmall, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bflags, B.d_bsmall + BS_FLAGS, 4, hipMemcpyDeviceToHost, st));
     if (host_out) HIPCHK(hipMemcpyAsync(out, dev_out, n * 4, hipMemcpyDeviceToHost, st));
     if (e->pool_nb) HIPCHK(hipMemcpyAsync(e->h_pool_next, e->d_pool_next, PC_WORDS * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (bflags & BF_TINY_FALLBACK) return TINY_FALLBACK;
-    if (bflags & BF_TINY_REJECTED) {  // rejected before any decision: submit_impl's checks, in its order
-        if (bflags & BF_BAD_RES) return fail(SG_EINVAL, "event res_id >= max_resources");
-        if (bflags & BF_BAD_REF)
-            return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
-        if (bflags & BF_TSPAN) return fail(SG_EINVAL, "a batch must span less than 2^31 ms");
-        if (bflags & BF_BACKWARD) return fail(SG_EINVAL, "event timestamps must be non-decreasing (SURVEY Q3)");
-        return fail(SG_EINVAL, "an sg_event_ext names args outside the table (or more than SG_MAX_ARGS, or a bad kind)");
-    }
+    // rejected before any decision: the group stage's checks, in their order (k_tiny raises the flag with one of them)
+    if (bflags & BF_TINY_REJECTED) return group_verdict(bflags);
     e->gbase += n;
     // the global inbound node: the two kernels of the batched path behind a call k_tiny decided (recs, dec and the
     // submission indices are in global memory); the caller's buffers are free again when this returns
     if (e->inb_on) {
         int64_t t0 = 0;
         HIPCHK(hipMemcpy(&t0, &dev_ev[0].ts, 8, hipMemcpyDeviceToHost));
-        HIPCHK(launch_inbound(e->d_recs, e->d_dec, n, dev_ev, e->d_v0, S, dc, t0, e->d_inbpart, e->d_inb, st));
+        HIPCHK(launch_inbound(B.d_recs, B.d_dec, n, dev_ev, B.d_v0, S, dc, t0, e->d_inbpart, e->d_inb, st));
         HIPCHK(hipStreamSynchronize(st));
     }
-    // the decide stage's own flags (collect)
-    if (bflags & BF_BAD_REF)
-        return fail(SG_EINVAL, "an EXIT/TRACE references an event that is not an earlier ENTRY of the same resource");
-    if (bflags & BF_BACKWARD) return fail(SG_EINVAL, "event timestamps must be non-decreasing across batches (SURVEY Q3)");
-    if (bflags & BF_AUX_FULL) return fail(SG_ECAPACITY, "origin/context node pool full (raise aux_node_capacity)");
-    if (bflags & BF_PQ_INVARIANT)
-        e->fatal = "internal error: a k_pq tile's presorted key subset did not match its accesses";
-    else if (bflags & BF_POOL_FULL)
-        e->fatal = "the hot-parameter map pool is used up (raise param_table_log2)";
-    else if (bflags & BF_PTAB_FULL)
-        e->fatal = "a hot-parameter map table could not place a key (its map holds a ghost entry)";
-    if (bflags & (BF_PQ_INVARIANT | BF_PTAB_FULL | BF_POOL_FULL)) return fail(SG_ECAPACITY, e->fatal + " -- engine unusable");
-    return SG_OK;
+    // the decide stage's own flags, as collect() reads them.  (Its BF_LITE_STALE check cannot fire here: only k_lite
+    // raises that flag, and k_tiny decides with lane_seg<16>.)
+    return decide_verdict(e, bflags);
 }
 
 int sg_submit_async(sg_engine* e, const sg_event* ev, uint64_t n, uint32_t* out) {
@@ -3885,18 +3574,17 @@ int sg_snapshot_metrics(sg_engine* e, int64_t now_ms, sg_metric_node* out, uint6
     // out may be device memory (e.g. the buffer an RCCL all-gather sends from): the kernels write it
     // directly, no staging buffer and no host round trip
     const bool dev_out = out && is_device_ptr(out);
-    if (!dev_out && cap > e->snap_cap) {
-        dfree(e->d_snap_out);
-        HIPCHK(hipMalloc(&e->d_snap_out, std::max<uint64_t>(cap, 1) * sizeof(sg_metric_node)));
-        e->snap_cap = cap;
-    }
-    if (!e->d_part) { int rc = ensure_batch(e, 1); if (rc) return rc; }
+    if (!dev_out && cap > e->snap_cap) HIPCHK(grow(e->d_snap_out, e->snap_cap, cap, 1));
+    // the count's scan partials: the d_part of a batch slot (drained: no batch is in it), which an engine that has
+    // taken no batch yet does not have
+    if (int rc = ensure_batch(e, 1)) return rc;
+    auto& scratch = e->slot[e->cur];
     e->snap_hi = std::max(e->snap_hi, now_ms - now_ms % 1000);  // k_snap_count writes the bucket of now (DevCfg.snap_hi)
     HIPCHK(launch_snapshot(e->d_minb, e->d_info, R, now_ms, e->cfg.statistic_max_rt, e->d_snap_cnt, e->d_snap_off,
-                           e->d_part, e->d_small + 3, dev_out ? out : e->d_snap_out, dev_out || out ? cap : 0,
+                           scratch.d_part, e->d_small + SM_SNAP_TOTAL, dev_out ? out : e->d_snap_out, dev_out || out ? cap : 0,
                            e->stream));
     uint32_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, e->d_small + 3, 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&total, e->d_small + SM_SNAP_TOTAL, 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     uint64_t k = std::min<uint64_t>(total, cap);
     if (k && out && !dev_out)
@@ -4035,29 +3723,60 @@ static int ensure_ns(sg_engine* e) {
     e->d_nslim = d;
     return SG_OK;
 }
-// The namespace-grouped limiter step: k_tok_classify left (namespace index, request) pairs in kin / vin; a stable
-// sort by namespace, then every namespace's limiter over its own run (cluster.hip 2').  On return kin / vin hold
-// the flow sort's pairs.  Scratch as launch_tok_limiter_par: the drained batch slot's arrays.
-static int tok_limiter_grouped(sg_engine* e, uint64_t n, uint32_t nflows, uint32_t*& kin, uint32_t*& vin,
-                               uint32_t*& kout, uint32_t*& vout) {
+// A token call's stable radix sort of n (key, request) pairs with keys 0..nkeys.  It writes the pair arrays it is
+// passed (kin / vin and kout / vout, which swap with every pass: on return kin / vin hold the sorted pairs) and
+// scratch.d_hist and scratch.d_part (the digit histograms and the scan's partials) of the borrowed slot.
+static int tok_sort(sg_engine* e, sg_engine::BatchSlot& scratch, uint64_t n, uint32_t nkeys, uint32_t*& kin,
+                    uint32_t*& vin, uint32_t*& kout, uint32_t*& vout) {
     hipStream_t st = e->stream;
-    const uint32_t nns = (uint32_t)e->ns_names.size();
     int bits = 1;
-    while (bits < 32 && (1ull << bits) <= nns) ++bits;  // keys 0..nns (nns = tries no limiter)
+    while (bits < 32 && (1ull << bits) <= nkeys) ++bits;
     const int passes = (bits + 7) / 8;
     const uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
     for (int p = 0; p < passes; ++p) {
-        HIPCHK(launch_radix_hist(kin, n, p * 8, e->d_hist, nblocks, st));
-        HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks * 256, e->d_part, nullptr, st));
-        HIPCHK(launch_radix_scatter(kin, vin, n, p * 8, e->d_hist, nblocks, kout, vout, nullptr, st));
+        HIPCHK(launch_radix_hist(kin, n, p * 8, scratch.d_hist, nblocks, st));
+        HIPCHK(launch_scan(scratch.d_hist, scratch.d_hist, (uint64_t)nblocks * 256, scratch.d_part, nullptr, st));
+        HIPCHK(launch_radix_scatter(kin, vin, n, p * 8, scratch.d_hist, nblocks, kout, vout, nullptr, st));
         std::swap(kin, kout);
         std::swap(vin, vout);
     }
-    HIPCHK(launch_tok_limiter_ns(e->d_treq, n, kin, vin, e->d_tfidx, nflows, e->d_nslim, e->d_nslimit, nns, kout, vout,
-                                 e->d_tres, e->d_flag, e->d_pos, e->d_order, e->d_prev, e->d_part, e->d_small + 8,
-                                 e->d_nsb, launch_scan, st));
-    std::swap(kin, kout);
-    std::swap(vin, vout);
+    return SG_OK;
+}
+// The limiter step of a token call and the sort of its requests by flow index, for both token calls.  The requests
+// are classified (k_tok_classify: e->d_tfidx, and for the grouped limiter the (namespace index, request) pairs in
+// scratch.d_k0 / d_v0).  grouped: several limiters -- a stable sort by namespace (nns = tries no limiter), then every
+// namespace's limiter over its own run (cluster.hip 2'); else the one limiter, parallel per 100 ms bucket, or with
+// one_wave on one wave.  Then, when flows are loaded, the sort by flow index (nflows = not for a flow).  On return
+// kin / vin hold the pairs as the flows' kernels read them.
+// scratch: the batch slot the call borrows.  It overwrites the slot's d_k0 / d_v0 / d_k1 / d_v1 (the pairs), d_hist
+// and d_part (the sorts and scans) and d_flag, d_pos, d_order, d_prev, d_dec, d_posof (the parallel limiters' n-word
+// arrays), so no batch may be in the slot: its last batch is decided, and the next group stage into it runs after the
+// call (drain() before the call, or BatchSlot::lent).
+static int tok_limit_sort(sg_engine* e, sg_engine::BatchSlot& scratch, uint64_t n, uint32_t nflows, bool grouped,
+                          bool one_wave, uint32_t*& kin, uint32_t*& vin) {
+    hipStream_t st = e->stream;
+    auto& X = scratch;
+    // GlobalRequestLimiter: a negative qpsAllowed stands for "no limiter registered" (tryPass -> true)
+    const double allowed = e->ns_limit[0] < 0 ? 1.0 / 0.0 : e->ns_limit[0];
+    uint32_t *kout = X.d_k1, *vout = X.d_v1;
+    kin = X.d_k0;
+    vin = X.d_v0;
+    if (grouped) {
+        const uint32_t nns = (uint32_t)e->ns_names.size();
+        if (int rc = tok_sort(e, X, n, nns, kin, vin, kout, vout)) return rc;
+        HIPCHK(launch_tok_limiter_ns(e->d_treq, n, kin, vin, e->d_tfidx, nflows, e->d_nslim, e->d_nslimit, nns, kout, vout,
+                                     e->d_tres, X.d_flag, X.d_pos, X.d_order, X.d_prev, X.d_part, e->d_small + SM_LIMITER,
+                                     e->d_nsb, st));
+        std::swap(kin, kout);
+        std::swap(vin, vout);
+    } else if (one_wave)
+        HIPCHK(launch_tok_limiter(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, X.d_k0, X.d_v0, e->d_tres, st));
+    else
+        HIPCHK(launch_tok_limiter_par(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, X.d_k0, X.d_v0, e->d_tres,
+                                      X.d_flag, X.d_pos, X.d_order, X.d_prev, X.d_dec, X.d_posof, X.d_part,
+                                      e->d_small + SM_LIMITER, st));
+    if (nflows)
+        if (int rc = tok_sort(e, X, n, nflows, kin, vin, kout, vout)) return rc;
     return SG_OK;
 }
 // CSlot.pad of a loaded flowId table := the flowIds' namespace indices
@@ -4269,7 +3988,7 @@ int sg_cluster_metrics(sg_engine* e, const char* ns, int64_t now_ms, uint32_t to
             std::swap(vin, vout);
         }
         HIPCHK(launch_cm_select(kin, vin, ncand, e->d_pflow, npf, e->d_cm_sum, e->d_cm_key, top_n, e->d_cm_bounds,
-                                e->d_cm_nch, e->d_cm_coff, e->d_cm_part, e->d_cm_psum, e->d_cm_pkey, prows, launch_scan,
+                                e->d_cm_nch, e->d_cm_coff, e->d_cm_part, e->d_cm_psum, e->d_cm_pkey, prows,
                                 e->cm_ev + 3, st));
         HIPCHK(hipEventRecord(e->cm_ev[5], st));
     }
@@ -4377,8 +4096,9 @@ int sg_param_key_value(sg_engine* e, uint64_t key, char* class_type, size_t clas
 
 // Batched DefaultTokenService.requestToken (see cluster.hip for the device steps), in two parts so that the decide
 // stage can issue a batch's own requests (embedded token server): tok_ensure makes room for n requests and the
-// tables a call reads, tok_device decides the n requests already in e->d_treq into e->d_tres.
-static int tok_ensure(sg_engine* e, uint64_t n) {
+// tables a call reads (tab / mask: its flowId table), tok_device decides the n requests already in e->d_treq into
+// e->d_tres.
+static int tok_ensure(sg_engine* e, uint64_t n, CSlot*& tab, uint32_t& mask) {
     int rc = ensure_batch(e, n);  // radix-sort scratch
     if (rc) return rc;
     if (n > e->tcap) {
@@ -4390,57 +4110,34 @@ static int tok_ensure(sg_engine* e, uint64_t n) {
         e->tcap = c;
     }
     if (int rc2 = ensure_ns(e)) return rc2;
-    if (!e->d_ctab) {  // no cluster rule loaded yet: an empty table
+    if (!tab) {  // no cluster rule of the call's kind loaded yet: an empty table
         CSlot t[16];
         for (auto& x : t) { x.key = 0; x.idx = 0xFFFFFFFFu; x.pad = 0; }
-        HIPCHK(hipMalloc(&e->d_ctab, sizeof(t)));
-        HIPCHK(hipMemcpy(e->d_ctab, t, sizeof(t), hipMemcpyHostToDevice));
-        e->ctab_mask = 15;
+        HIPCHK(hipMalloc(&tab, sizeof(t)));
+        HIPCHK(hipMemcpy(tab, t, sizeof(t), hipMemcpyHostToDevice));
+        mask = 15;
     }
     return SG_OK;
 }
-// The requests are in time order and their tables exist (tok_ensure).  The active batch slot's arrays (activate()) are
-// the call's scratch: no batch may be using them.  The classification's flag is read back on the host, so every
-// earlier kernel of the engine stream is done when this returns; the flows' kernels may still be running.
-static int tok_device(sg_engine* e, uint64_t n) {
+// The requests are in time order and their tables exist (tok_ensure).  scratch: the batch slot whose arrays the call
+// overwrites (tok_limit_sort).  The classification's flag is read back on the host, so every earlier kernel of the
+// engine stream is done when this returns; the flows' kernels may still be running.
+static int tok_device(sg_engine* e, sg_engine::BatchSlot& scratch, uint64_t n) {
     hipStream_t st = e->stream;
     const uint32_t nflows = (uint32_t)e->cflows.size();
-    HIPCHK(hipMemsetAsync(e->d_small, 0, 4, st));
+    HIPCHK(hipMemsetAsync(e->d_small + SM_FLAGS, 0, 4, st));
     const uint32_t nns = (uint32_t)e->ns_names.size();
     const bool grouped = nns > 1 || e->tok_ns;  // several limiters: the namespace-grouped limiter step
-    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_ctab, e->ctab_mask, e->d_tfidx, e->d_tres, e->d_small,
-                               grouped ? e->d_k0 : nullptr, grouped ? e->d_v0 : nullptr, nns, st));
+    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_ctab, e->ctab_mask, e->d_tfidx, e->d_tres, e->d_small + SM_FLAGS,
+                               grouped ? scratch.d_k0 : nullptr, grouped ? scratch.d_v0 : nullptr, nns, st));
     uint32_t flags = 0;
-    HIPCHK(hipMemcpyAsync(&flags, e->d_small, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&flags, e->d_small + SM_FLAGS, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (flags & 1) return fail(SG_EINVAL, "token requests must be ordered by ts (the replay clock)");
-    // GlobalRequestLimiter: a negative qpsAllowed stands for "no limiter registered" (tryPass -> true)
-    const double allowed = e->ns_limit[0] < 0 ? 1.0 / 0.0 : e->ns_limit[0];
-    // the limiter (parallel per 100 ms bucket; the batch slot's arrays are its scratch), then the flows
-    uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
-    if (grouped) {
-        if (int rc2 = tok_limiter_grouped(e, n, nflows, kin, vin, kout, vout)) return rc2;
-    } else
-        HIPCHK(launch_tok_limiter_par(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0,
-                                      e->d_tres, e->d_flag, e->d_pos, e->d_order, e->d_prev, e->d_dec, e->d_posof,
-                                      e->d_part, e->d_small + 8, launch_scan, st));
+    uint32_t *kin, *vin;
+    if (int rc = tok_limit_sort(e, scratch, n, nflows, grouped, false, kin, vin)) return rc;
     if (nflows) {
-        int bits = 1;
-        while (bits < 32 && (1ull << bits) <= nflows) ++bits;  // keys 0..nflows (nflows = not for a flow)
-        const int passes = (bits + 7) / 8;
-        const uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
-        for (int p = 0; p < passes; ++p) {
-            HIPCHK(launch_radix_hist(kin, n, p * 8, e->d_hist, nblocks, st));
-            HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks * 256, e->d_part, nullptr, st));
-            HIPCHK(launch_radix_scatter(kin, vin, n, p * 8, e->d_hist, nblocks, kout, vout, nullptr, st));
-            std::swap(kin, kout);
-            std::swap(vin, vout);
-        }
-        if (nflows + 1 > e->tbounds_cap) {
-            dfree(e->d_tbounds);
-            e->tbounds_cap = std::max<uint32_t>(nflows + 1, 1u << 12);
-            HIPCHK(hipMalloc(&e->d_tbounds, (uint64_t)e->tbounds_cap * 4));
-        }
+        if (nflows + 1 > e->tbounds_cap) HIPCHK(grow(e->d_tbounds, e->tbounds_cap, nflows + 1, 1u << 12));
         // (the other decide streams are idle: every earlier batch is decided, see above)
         HIPCHK(launch_tok_flow(kin, vin, n, e->d_treq, e->d_cflow, nflows, e->d_cbkt, e->cfg.cluster_exceed_count,
                                e->cfg.cluster_max_occupy_ratio, e->d_tres, e->d_tbounds, e->tok_light, e->tok_wide, st,
@@ -4454,10 +4151,10 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
     if (n > 0x7FFFFFFFull) return fail(SG_EINVAL, "too many token requests in one call");
     if (int rc = drain(e)) return rc;
     hipStream_t st = e->stream;
-    if (int rc = tok_ensure(e, n)) return rc;
+    if (int rc = tok_ensure(e, n, e->d_ctab, e->ctab_mask)) return rc;
     // requests and results may be host or device memory (dist.request_tokens keeps them in HBM under RCCL)
     HIPCHK(hipMemcpyAsync(e->d_treq, reqs, n * sizeof(sg_token_req), hipMemcpyDefault, st));
-    if (int rc = tok_device(e, n)) return rc;
+    if (int rc = tok_device(e, e->slot[e->cur], n)) return rc;  // (drained: no batch is in either slot)
     HIPCHK(hipMemcpyAsync(out, e->d_tres, n * sizeof(sg_token_result), hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));
     return SG_OK;
@@ -4466,7 +4163,7 @@ int sg_cluster_request_tokens(sg_engine* e, const sg_token_req* reqs, uint64_t n
 // Embedded token server, the decide stage's step for batch slot k (decide_enqueue, after the chain grants): the
 // ENTRYs that ask for a token are compacted in submission order into e->d_treq (kernels.hip k_emb_count /
 // k_emb_scatter, the test in embedded.h), one token call decides them, and k_emb_answers leaves each answer's side
-// word at the ENTRY's sorted position (e->d_emb_side, cleared first) and counts the answers (d_bsmall[101..107]; [100]
+// word at the ENTRY's sorted position (e->d_emb_side, cleared first) and counts the answers (BS_EMB_ANS ..; BS_EMB_REQ
 // the requests).  The token call's scratch is the other slot's arrays: its batch is decided (submit_impl hands a batch
 // with XF_EMB events off before the next group stage is enqueued), and the call runs on the engine stream behind it.
 // The host waits twice (the request count, the classification's flag): such a batch overlaps with no neighbour.
@@ -4491,21 +4188,18 @@ static int embedded_tokens(sg_engine* e, int k, uint32_t* nreq_out) {
     e->emb_timed = false;
     HIPCHK(hipEventRecord(e->emb_t[0], st));
     HIPCHK(launch_emb_count(G.dev_ev, G.dev_ext, n, e->cfg.max_resources, SG_MAX_CONTEXTS, e->d_prog, e->d_info, dev_auth(e),
-                            dev_auth_ids(e), e->cfg.switch_on, e->d_emb_cnt, e->d_emb_part, bs + 100, st));
+                            dev_auth_ids(e), e->cfg.switch_on, e->d_emb_cnt, e->d_emb_part, bs + BS_EMB_REQ, st));
     uint32_t nreq = 0;
-    HIPCHK(hipMemcpyAsync(&nreq, bs + 100, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&nreq, bs + BS_EMB_REQ, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *nreq_out = nreq;
     if (!nreq) return SG_OK;
-    if (int rc = tok_ensure(e, nreq)) return rc;  // (nreq <= n <= cap_n: the batch arrays stay)
+    if (int rc = tok_ensure(e, nreq, e->d_ctab, e->ctab_mask)) return rc;  // (nreq <= n <= cap_n: the batch arrays stay)
     HIPCHK(launch_emb_scatter(G.dev_ev, G.dev_ext, n, e->cfg.max_resources, SG_MAX_CONTEXTS, e->d_prog, e->d_info,
                               dev_auth(e), dev_auth_ids(e), e->cfg.switch_on, e->d_emb_cnt, e->d_emb_flow, nreq, e->d_treq,
                               e->d_emb_idx, st));
     HIPCHK(hipEventRecord(e->emb_t[1], st));
-    activate(e, k ^ 1);
-    const int rc = tok_device(e, nreq);
-    activate(e, k);
-    if (rc) return rc;
+    if (int rc = tok_device(e, e->slot[k ^ 1], nreq)) return rc;
     // the call's last kernels are still in flight: the next group stage into the borrowed slot waits for them
     if (!e->emb_ev[k ^ 1]) HIPCHK(hipEventCreateWithFlags(&e->emb_ev[k ^ 1], hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->emb_ev[k ^ 1], st));
@@ -4513,7 +4207,7 @@ static int embedded_tokens(sg_engine* e, int k, uint32_t* nreq_out) {
     HIPCHK(hipEventRecord(e->emb_t[2], st));
     HIPCHK(hipMemsetAsync(e->d_emb_side, 0, n * 4, st));
     HIPCHK(launch_emb_answers(e->d_tres, e->d_emb_idx, nreq, B.radix ? B.d_posof : nullptr, B.d_flag, B.d_pos, B.nhot, n,
-                              e->d_emb_side, bs + 101, st));
+                              e->d_emb_side, bs + BS_EMB_ANS, st));
     HIPCHK(hipEventRecord(e->emb_t[3], st));
     e->emb_timed = true;
     return SG_OK;
@@ -4639,131 +4333,67 @@ int sg_cluster_request_param_tokens(sg_engine* e, const sg_param_token_req* reqs
     if (n > 0x7FFFFFFFull) return fail(SG_EINVAL, "too many token requests in one call");
     if (int rc = drain(e)) return rc;
     hipStream_t st = e->stream;
-    int rc = ensure_batch(e, n);
-    if (rc) return rc;
-    if (n > e->tcap) {
-        dfree(e->d_treq); dfree(e->d_tres); dfree(e->d_tfidx);
-        e->d_treq = nullptr; e->d_tres = nullptr; e->d_tfidx = nullptr;
-        e->tcap = 0;
-        uint64_t c = std::max<uint64_t>(n, 1u << 16);
-        HIPCHK(hipMalloc(&e->d_treq, c * sizeof(sg_token_req)));
-        HIPCHK(hipMalloc(&e->d_tres, c * sizeof(sg_token_result)));
-        HIPCHK(hipMalloc(&e->d_tfidx, c * 4));
-        e->tcap = c;
-    }
-    if (n > e->pcap) {
-        dfree(e->d_preq);
-        e->d_preq = nullptr;
-        e->pcap = 0;
-        const uint64_t c = std::max<uint64_t>(n, 1u << 16);
-        HIPCHK(hipMalloc(&e->d_preq, c * sizeof(sg_param_token_req)));
-        e->pcap = c;
-    }
-    if (n_values > e->pvcap) {
-        dfree(e->d_pvals);
-        e->d_pvals = nullptr;
-        e->pvcap = 0;
-        const uint64_t c = std::max<uint64_t>(n_values, 1u << 16);
-        HIPCHK(hipMalloc(&e->d_pvals, c * sizeof(uint64_t)));
-        e->pvcap = c;
-    }
+    if (int rc = tok_ensure(e, n, e->d_pftab, e->pftab_mask)) return rc;
+    if (n > e->pcap) HIPCHK(grow(e->d_preq, e->pcap, n, 1u << 16));
+    if (n_values > e->pvcap) HIPCHK(grow(e->d_pvals, e->pvcap, n_values, 1u << 16));
     if (!e->d_ptst) {
         HIPCHK(hipMalloc(&e->d_ptst, 8 * sizeof(unsigned long long)));
         HIPCHK(hipMemset(e->d_ptst, 0, 8 * sizeof(unsigned long long)));
     }
     const uint32_t nflows = (uint32_t)e->pflows.size();
-    if (nflows > e->ptserial_cap) {
-        dfree(e->d_ptserial);
-        e->d_ptserial = nullptr;
-        e->ptserial_cap = 0;
-        const uint64_t c = std::max<uint64_t>(nflows, 1u << 12);
-        HIPCHK(hipMalloc(&e->d_ptserial, c * 4));
-        e->ptserial_cap = c;
-    }
+    if (nflows > e->ptserial_cap) HIPCHK(grow(e->d_ptserial, e->ptserial_cap, nflows, 1u << 12));
     uint64_t dcap = 1u << 12;  // the dedup table: a power of two of at least twice the call's requests
     while (dcap < 2 * n) dcap <<= 1;
-    if (dcap > e->ptdedup_cap) {
-        dfree(e->d_ptdedup);
-        e->d_ptdedup = nullptr;
-        e->ptdedup_cap = 0;
-        HIPCHK(hipMalloc(&e->d_ptdedup, dcap * 4));
-        e->ptdedup_cap = dcap;
-    }
-    if (int rc2 = ensure_ns(e)) return rc2;
-    if (!e->d_pftab) {  // no cluster param rule loaded yet: an empty table
-        CSlot t[16];
-        for (auto& x : t) { x.key = 0; x.idx = 0xFFFFFFFFu; x.pad = 0; }
-        HIPCHK(hipMalloc(&e->d_pftab, sizeof(t)));
-        HIPCHK(hipMemcpy(e->d_pftab, t, sizeof(t), hipMemcpyHostToDevice));
-        e->pftab_mask = 15;
-    }
+    if (dcap > e->ptdedup_cap) HIPCHK(grow(e->d_ptdedup, e->ptdedup_cap, dcap, 0));
+    auto& X = e->slot[e->cur];  // the call's scratch (tok_limit_sort; drained: no batch is in either slot)
+    uint32_t* d_flags = e->d_small + SM_FLAGS;
     // the request view, the range check and the listed values, on the device, then the classify step (it writes
     // the call's own arrays only); (range flag, listed) and the order flag are read once, before anything moves
     HIPCHK(hipMemcpyAsync(e->d_preq, reqs, n * sizeof(sg_param_token_req), hipMemcpyDefault, st));
     if (n_values) HIPCHK(hipMemcpyAsync(e->d_pvals, values, n_values * sizeof(uint64_t), hipMemcpyDefault, st));
     HIPCHK(hipMemsetAsync(e->d_ptst, 0, 2 * sizeof(unsigned long long), st));
-    HIPCHK(hipMemsetAsync(e->d_small, 0, 4, st));
+    HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
     HIPCHK(launch_ptok_prep(e->d_preq, n, n_values, e->d_treq, e->d_ptst, st));
     const uint32_t nns = (uint32_t)e->ns_names.size();
     const bool grouped = nns > 1 || e->tok_ns;
-    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_pftab, e->pftab_mask, e->d_tfidx, e->d_tres, e->d_small,
-                               grouped ? e->d_k0 : nullptr, grouped ? e->d_v0 : nullptr, nns, st));
-    unsigned long long head[2] = {0, 0};
+    HIPCHK(launch_tok_classify(e->d_treq, n, e->d_pftab, e->pftab_mask, e->d_tfidx, e->d_tres, d_flags,
+                               grouped ? X.d_k0 : nullptr, grouped ? X.d_v0 : nullptr, nns, st));
+    unsigned long long pst[2] = {0, 0};
     uint32_t flags = 0;
-    HIPCHK(hipMemcpyAsync(head, e->d_ptst, sizeof(head), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&flags, e->d_small, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pst, e->d_ptst, sizeof(pst), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (head[1] & 1) return fail(SG_EINVAL, "param token request values out of range");
+    if (pst[1] & 1) return fail(SG_EINVAL, "param token request values out of range");
     if (flags & 1) return fail(SG_EINVAL, "token requests must be ordered by ts (the replay clock)");
-    const uint64_t listed = head[0];  // the call claims at most that many value slots
+    const uint64_t listed = pst[0];  // the call claims at most that many value slots
     if (int rc2 = pv_make_room(e, listed)) return rc2;  // before the limiter or any window moves
-    const double allowed = e->ns_limit[0] < 0 ? 1.0 / 0.0 : e->ns_limit[0];
-    uint32_t *kin = e->d_k0, *vin = e->d_v0, *kout = e->d_k1, *vout = e->d_v1;
     // A small call spread thinly over many flows (fewer than SG_PTOK_MIN requests and fewer than PTOK_PER_FLOW per
     // loaded flow) keeps the one-wave limiter and k_ptok_flow for every flow: fewer launches than the parallel
     // limiter and the value-parallel owner need, and a lane's walk is short there (measured).
     constexpr uint64_t PTOK_PER_FLOW = 8;
     const bool small = n < e->ptok_min && n < PTOK_PER_FLOW * nflows;
     const bool lane_only = !e->ptok_vp || small;
-    if (grouped) {
-        if (int rc2 = tok_limiter_grouped(e, n, nflows, kin, vin, kout, vout)) return rc2;
-    } else if (small)
-        HIPCHK(launch_tok_limiter(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0, e->d_tres,
-                                  st));
-    else
-        HIPCHK(launch_tok_limiter_par(e->d_treq, n, e->d_tfidx, nflows, e->d_nslim, allowed, e->d_k0, e->d_v0,
-                                      e->d_tres, e->d_flag, e->d_pos, e->d_order, e->d_prev, e->d_dec, e->d_posof,
-                                      e->d_part, e->d_small + 8, launch_scan, st));
+    uint32_t *kin, *vin;
+    if (int rc2 = tok_limit_sort(e, X, n, nflows, grouped, small, kin, vin)) return rc2;
     if (nflows) {
-        int bits = 1;
-        while (bits < 32 && (1ull << bits) <= nflows) ++bits;
-        const int passes = (bits + 7) / 8;
-        const uint32_t nblocks = (uint32_t)((n + radix_tile() - 1) / radix_tile());
-        for (int p = 0; p < passes; ++p) {
-            HIPCHK(launch_radix_hist(kin, n, p * 8, e->d_hist, nblocks, st));
-            HIPCHK(launch_scan(e->d_hist, e->d_hist, (uint64_t)nblocks * 256, e->d_part, nullptr, st));
-            HIPCHK(launch_radix_scatter(kin, vin, n, p * 8, e->d_hist, nblocks, kout, vout, nullptr, st));
-            std::swap(kin, kout);
-            std::swap(vin, vout);
-        }
         e->pv_claimed += listed;
         if (lane_only)
             HIPCHK(launch_ptok_flow(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab,
-                                    e->pv_mask, e->d_tres, e->d_small, nullptr, e->d_ptst + 2, st));
+                                    e->pv_mask, e->d_tres, d_flags, nullptr, e->d_ptst + 2, st));
         else {
             // who decides which flow; the two owners then work on disjoint flows (the limiter's scratch arrays are free)
             HIPCHK(launch_ptok_elig(kin, vin, n, e->d_preq, e->d_pflow, nflows, e->d_ptserial, st));
             HIPCHK(launch_ptok_flow(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab,
-                                    e->pv_mask, e->d_tres, e->d_small, e->d_ptserial, nullptr, st));
+                                    e->pv_mask, e->d_tres, d_flags, e->d_ptserial, nullptr, st));
             HIPCHK(launch_ptok_vp(kin, vin, n, e->d_preq, e->d_pvals, e->d_pflow, nflows, e->d_phot, e->d_pvtab, e->pv_mask,
-                                  e->d_ptserial, e->d_ptdedup, (uint32_t)(dcap - 1), e->d_flag, e->d_pos, e->d_order,
-                                  e->d_prev, e->d_dec, e->d_posof, reinterpret_cast<int64_t*>(e->d_cand),
-                                  reinterpret_cast<int32_t*>(e->d_out), e->d_hist, e->d_part, radix_tile(), e->d_tres,
-                                  e->d_small, e->d_ptst + 2, launch_radix_hist, launch_radix_scatter, launch_scan, st));
+                                  e->d_ptserial, e->d_ptdedup, (uint32_t)(dcap - 1), X.d_flag, X.d_pos, X.d_order,
+                                  X.d_prev, X.d_dec, X.d_posof, reinterpret_cast<int64_t*>(X.d_cand),
+                                  reinterpret_cast<int32_t*>(X.d_out), X.d_hist, X.d_part, radix_tile(), e->d_tres,
+                                  d_flags, e->d_ptst + 2, st));
         }
     }
     HIPCHK(hipMemcpyAsync(out, e->d_tres, n * sizeof(sg_token_result), hipMemcpyDefault, st));
-    HIPCHK(hipMemcpyAsync(&flags, e->d_small, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (flags & 2) return fail(SG_ENOMEM, "cluster param value table is full");
     return SG_OK;

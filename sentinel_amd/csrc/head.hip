@@ -31,6 +31,7 @@
 // (head_seg below); one launch takes both kinds (k_head).
 #include "chain.h"
 #include "dev_types.h"
+#include "launch.h"
 
 namespace sg {
 

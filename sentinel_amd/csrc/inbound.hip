@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "aux.h"
+#include "launch.h"
 
 using namespace sg;
 

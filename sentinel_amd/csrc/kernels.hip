@@ -15,6 +15,7 @@
 #include "authority.h"
 #include "dev_types.h"
 #include "embedded.h"
+#include "launch.h"
 
 using namespace sg;
 

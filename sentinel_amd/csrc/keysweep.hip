@@ -20,6 +20,7 @@
 
 #include "chain.h"
 #include "dev_types.h"
+#include "launch.h"
 #include "pmap.h"
 
 namespace sg {

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "chain.h"
+#include "launch.h"
 #include "pmap.h"
 
 using namespace sg;
@@ -1713,8 +1714,6 @@ __global__ __launch_bounds__(256) void k_pc_back(PBucket* __restrict__ b1, PData
 }
 
 namespace sg {
-hipError_t launch_scan_n(const uint32_t* in, uint32_t* out, uint64_t n, const uint32_t* ndev, uint32_t* part,
-                         uint32_t* total, hipStream_t st);  // kernels.hip
 // mv / nmv / mcap: the move list (null: each lane moves its maps itself)
 // The batch's map growth (pool_next = the pool's control words): a first pass; then, only if that pass found the pool
 // short, the compaction into the other pool (b2 / d2), its copy back and a second pass (every kernel of the rescue
@@ -1722,7 +1721,6 @@ hipError_t launch_scan_n(const uint32_t* in, uint32_t* out, uint64_t n, const ui
 hipError_t launch_pm_grow(const Seg* segs, const uint32_t* mp, uint32_t mb, const DevState& S, unsigned long long* pool_next,
                           uint64_t pool_nb, uint32_t* bflags, uint4* mv, uint32_t* nmv, uint32_t mcap, uint32_t epoch,
                           uint32_t nm, PBucket* b2, PData* d2, uint32_t* sz, uint32_t* off, uint32_t* part,
-                          hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
                           hipStream_t st) {
     if (!mb) return hipSuccess;
     if (!mcap) mv = nullptr;
@@ -1752,12 +1750,11 @@ hipError_t launch_pm_grow(const Seg* segs, const uint32_t* mp, uint32_t mb, cons
 // sz / off: n words each; part: scan partials
 hipError_t launch_pm_compact(PMap* pm, uint32_t n, const PBucket* ob, const PData* od, PBucket* nbk, PData* nd,
                              uint32_t* sz, uint32_t* off, uint32_t* part, unsigned long long* pool_next,
-                             hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
                              hipStream_t st) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_pc_nb, dim3(std::min<uint32_t>((n + 255) / 256, 1024u)), dim3(256), 0, st, pm, n, sz,
                        (const unsigned long long*)nullptr, 0u, (uint32_t*)nullptr);
-    const hipError_t e = scan(sz, off, n, part, nullptr, st);
+    const hipError_t e = launch_scan(sz, off, n, part, nullptr, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pc_copy, dim3(std::min<uint32_t>((n + 3) / 4, 2048u)), dim3(256), 0, st, pm, n, off, ob, od, nbk,
                        nd, pool_next, 0u, 0u);

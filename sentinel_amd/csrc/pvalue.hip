@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "chain.h"
+#include "launch.h"
 #include "pmap.h"
 
 using namespace sg;
@@ -1167,10 +1168,6 @@ __global__ __launch_bounds__(1024) void k_pv_commit(PvBuf B, const PvSeg* __rest
 namespace sg {
 // the accesses [0, tot) by group id, stable (tot on the device: the tiles past it idle; pads [tot, cap))
 static hipError_t pv_sort(PvBuf B, uint32_t cap, uint32_t* tot, uint32_t* hist, uint32_t* part, hipStream_t st,
-                          hipError_t (*radix_hist)(const uint32_t*, uint64_t, const uint32_t*, int, uint32_t*, uint32_t, hipStream_t),
-                          hipError_t (*radix_scatter)(const uint32_t*, const uint32_t*, uint64_t, const uint32_t*, int,
-                                                      const uint32_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t),
-                          hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
                           uint32_t tile) {
     hipError_t e = hipSuccess;
     const uint32_t nb = (cap + 255) / 256;
@@ -1182,9 +1179,9 @@ static hipError_t pv_sort(PvBuf B, uint32_t cap, uint32_t* tot, uint32_t* hist, 
     const uint32_t nblocks = (cap + tile - 1) / tile;
     uint32_t *kin = B.gid, *vin = B.idx, *kout = B.gid2, *vout = B.idx2;
     for (int p = 0; p < passes; ++p) {
-        e = radix_hist(kin, cap, tot, p * 8, hist, nblocks, st);
-        if (e == hipSuccess) e = scan(hist, hist, (uint64_t)nblocks << 8, part, nullptr, st);
-        if (e == hipSuccess) e = radix_scatter(kin, vin, cap, tot, p * 8, hist, nblocks, kout, vout, st);
+        e = launch_radix_hist_n(kin, cap, tot, p * 8, hist, nblocks, st);
+        if (e == hipSuccess) e = launch_scan(hist, hist, (uint64_t)nblocks << 8, part, nullptr, st);
+        if (e == hipSuccess) e = launch_radix_scatter_n(kin, vin, cap, tot, p * 8, hist, nblocks, kout, vout, st);
         if (e != hipSuccess) return e;
         uint32_t* tk = kin; kin = kout; kout = tk;
         uint32_t* tv = vin; vin = vout; vout = tv;
@@ -1197,14 +1194,11 @@ static hipError_t pv_sort(PvBuf B, uint32_t cap, uint32_t* tot, uint32_t* hist, 
     return hipSuccess;
 }
 
-// the scans below run over the accesses only (tot[0] on the device), not the scratch capacity (kernels.hip)
-hipError_t launch_scan_n(const uint32_t* in, uint32_t* out, uint64_t n, const uint32_t* ndev, uint32_t* part,
-                         uint32_t* total, hipStream_t st);
+// the scans below run over the accesses only (tot[0] on the device), not the scratch capacity (launch_scan_n)
 
 // residency (after k_pv_prev / k_pv_blocks): NF / NN prefix counts in gdt / gaw, horizons in gpos
 static hipError_t pv_resid(PvBuf B, uint32_t cap, uint32_t* tot, const PvSeg* pv, const DevState& S, uint32_t* part,
-                           hipStream_t st,
-                           hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t)) {
+                           hipStream_t st) {
     const uint32_t nb = (cap + 255) / 256, nblk = (cap + PV_B - 1) / PV_B;
     uint32_t* nf = reinterpret_cast<uint32_t*>(B.gdt);
     hipLaunchKernelGGL(k_pv_fflags, dim3(nb), dim3(256), 0, st, B, tot, cap);
@@ -1218,8 +1212,7 @@ static hipError_t pv_resid(PvBuf B, uint32_t cap, uint32_t* tot, const PvSeg* pv
 
 // the commit's kept list (gdt: exclusive scan of the keep flags, idx2: the list) and the touched stamps' removal
 static hipError_t pv_klist(PvBuf B, uint32_t cap, uint32_t* tot, const PvSeg* pv, const DevState& S, uint32_t tmode,
-                           uint32_t* part, hipStream_t st,
-                           hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t)) {
+                           uint32_t* part, hipStream_t st) {
     const uint32_t nb = (cap + 255) / 256;
     hipLaunchKernelGGL(k_pv_keepw, dim3(nb), dim3(256), 0, st, B, tot, cap);
     const hipError_t e = launch_scan_n(reinterpret_cast<const uint32_t*>(B.tc), reinterpret_cast<uint32_t*>(B.gdt), cap,
@@ -1237,12 +1230,8 @@ static hipError_t pv_klist(PvBuf B, uint32_t cap, uint32_t* tot, const PvSeg* pv
 // jumps: the batch has no zero-acquire ENTRY.
 hipError_t launch_pv_a(SEv* recs, const uint32_t* vals, Seg* segs, const uint32_t* list, uint32_t m,
                        const DevState& S, const DevCfg& cfg, uint32_t* dec, PvSeg* pv, PvBuf B, uint32_t cap,
-                       uint32_t* tot, uint32_t* hist, uint32_t* part, hipStream_t st,
-                       hipError_t (*radix_hist)(const uint32_t*, uint64_t, const uint32_t*, int, uint32_t*, uint32_t, hipStream_t),
-                       hipError_t (*radix_scatter)(const uint32_t*, const uint32_t*, uint64_t, const uint32_t*, int,
-                                                   const uint32_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t),
-                       hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                       uint32_t tile, uint32_t* rest, uint32_t grant_all) {
+                       uint32_t* tot, uint32_t* hist, uint32_t* part, hipStream_t st, uint32_t tile, uint32_t* rest,
+                       uint32_t grant_all) {
     if (!m || !cap) return hipSuccess;
     const uint32_t nchunk = cap / PV_CH + m + 1;
     hipError_t e = hipMemsetAsync(tot, 0, 16, st);
@@ -1255,20 +1244,18 @@ hipError_t launch_pv_a(SEv* recs, const uint32_t* vals, Seg* segs, const uint32_
     hipLaunchKernelGGL(k_pv_count, dim3(nchunk), dim3(256), 0, st, recs, vals, segs, list, S, cfg, pv, B, tot, dec);
     hipLaunchKernelGGL(k_pv_offsets, dim3(1), dim3(256), 0, st, pv, m, B, tot);
     hipLaunchKernelGGL(k_pv_fill, dim3(nchunk), dim3(256), 0, st, recs, vals, segs, list, S, cfg, pv, B, tot);
-    return pv_sort(B, cap, tot, hist, part, st, radix_hist, radix_scatter, scan, tile);
+    return pv_sort(B, cap, tot, hist, part, st, tile);
 }
 hipError_t launch_pv_b(SEv* recs, Seg* segs, const uint32_t* list, uint32_t m, const DevState& S, int64_t t0,
                        uint32_t* dec, uint32_t* bflags, PvSeg* pv, PvBuf B, uint32_t cap, uint32_t* tot, uint32_t* part,
-                       uint32_t jumps, hipStream_t st,
-                       hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                       uint32_t* rest) {
+                       uint32_t jumps, hipStream_t st, uint32_t* rest) {
     if (!m || !cap) return hipSuccess;
     hipError_t e = hipSuccess;
     const uint32_t nb = (cap + 255) / 256;
     hipLaunchKernelGGL(k_pv_rpre, dim3(m), dim3(256), 0, st, pv, m, S);
     hipLaunchKernelGGL(k_pv_prev, dim3(nb), dim3(256), 0, st, B, tot, pv, S);
     hipLaunchKernelGGL(k_pv_blocks, dim3((cap + PV_B - 1) / PV_B), dim3(PV_B), 0, st, B, tot);
-    e = pv_resid(B, cap, tot, pv, S, part, st, scan);
+    e = pv_resid(B, cap, tot, pv, S, part, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pv_gather, dim3(nb), dim3(256), 0, st, segs, list, B, tot);
     {   // MC in place (its values up to tot read only the flags before them)
@@ -1284,7 +1271,7 @@ hipError_t launch_pv_b(SEv* recs, Seg* segs, const uint32_t* list, uint32_t m, c
     hipLaunchKernelGGL(k_pv_walk, dim3(nb), dim3(256), 0, st, recs, segs, list, B, tot, pv, S, t0, dec, jumps, cap, bflags,
                        B.idx2);
     hipLaunchKernelGGL(k_pv_ranges, dim3(2048), dim3(256), 0, st, recs, B, tot, cap, dec);
-    e = pv_klist(B, cap, tot, pv, S, 0u, part, st, scan);
+    e = pv_klist(B, cap, tot, pv, S, 0u, part, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pv_commit, dim3(m), dim3(1024), 0, st, B, pv, m, S, bflags, 0u, segs, list,
                        reinterpret_cast<const uint32_t*>(B.gdt), B.idx2, nullptr, rest);
@@ -1295,12 +1282,8 @@ hipError_t launch_pv_b(SEv* recs, Seg* segs, const uint32_t* list, uint32_t m, c
 // segments with SEG_PVT); tot: 4 device words of its own
 hipError_t launch_pvt(SEv* recs, const sg_event* ev, const uint32_t* vals, Seg* segs, const uint32_t* list, uint32_t m,
                       const DevState& S, const DevCfg& cfg, uint32_t* dec, uint32_t* bflags, PvSeg* pv, PvBuf B,
-                      uint32_t cap, uint32_t* tot, uint32_t* hist, uint32_t* part, hipStream_t st,
-                      hipError_t (*radix_hist)(const uint32_t*, uint64_t, const uint32_t*, int, uint32_t*, uint32_t, hipStream_t),
-                      hipError_t (*radix_scatter)(const uint32_t*, const uint32_t*, uint64_t, const uint32_t*, int,
-                                                      const uint32_t*, uint32_t, uint32_t*, uint32_t*, hipStream_t),
-                      hipError_t (*scan)(const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, hipStream_t),
-                      uint32_t tile, uint32_t* rest) {
+                      uint32_t cap, uint32_t* tot, uint32_t* hist, uint32_t* part, hipStream_t st, uint32_t tile,
+                      uint32_t* rest) {
     if (!m || !cap) return hipSuccess;
     const uint32_t nchunk = cap / PV_CH + m + 1;
     hipError_t e = hipMemsetAsync(tot, 0, 16, st);
@@ -1314,12 +1297,12 @@ hipError_t launch_pvt(SEv* recs, const sg_event* ev, const uint32_t* vals, Seg* 
     hipLaunchKernelGGL(k_pvt_count, dim3(nchunk), dim3(256), 0, st, recs, ev, vals, segs, list, S, cfg, pv, B, tot, dec);
     hipLaunchKernelGGL(k_pv_offsets, dim3(1), dim3(256), 0, st, pv, m, B, tot);
     hipLaunchKernelGGL(k_pvt_fill, dim3(nchunk), dim3(256), 0, st, recs, ev, vals, segs, list, S, cfg, pv, B, tot, dec);
-    e = pv_sort(B, cap, tot, hist, part, st, radix_hist, radix_scatter, scan, tile);
+    e = pv_sort(B, cap, tot, hist, part, st, tile);
     if (e != hipSuccess) return e;
     const uint32_t nb = (cap + 255) / 256;
     hipLaunchKernelGGL(k_pv_prev, dim3(nb), dim3(256), 0, st, B, tot, pv, S);
     hipLaunchKernelGGL(k_pv_blocks, dim3((cap + PV_B - 1) / PV_B), dim3(PV_B), 0, st, B, tot);
-    e = pv_resid(B, cap, tot, pv, S, part, st, scan);
+    e = pv_resid(B, cap, tot, pv, S, part, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pvt_walk, dim3(nb), dim3(256), 0, st, B, tot, pv, S);
     // (the peak of the segments with releases; the scan's output in gdt: free in the post pass)
@@ -1327,7 +1310,7 @@ hipError_t launch_pvt(SEv* recs, const sg_event* ev, const uint32_t* vals, Seg* 
                       nullptr, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pvt_peak, dim3(nb), dim3(256), 0, st, B, reinterpret_cast<const uint32_t*>(B.gdt), tot, pv);
-    e = pv_klist(B, cap, tot, pv, S, 1u, part, st, scan);
+    e = pv_klist(B, cap, tot, pv, S, 1u, part, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pv_commit, dim3(m), dim3(1024), 0, st, B, pv, m, S, bflags, 1u, segs, list,
                        reinterpret_cast<const uint32_t*>(B.gdt), B.idx2, tot + 3, rest);
