@@ -1,8 +1,11 @@
 // engine.cpp -- host side of the MI355X decision engine: the C ABI of
-// include/sentinel_gpu.h, the rule managers (validation, de-duplication,
-// java.util.HashSet ordering, FlowRuleComparator sort) and the per-batch
-// launch pipeline.  All decisions are taken by the HIP kernels in kernels.hip;
-// nothing here evaluates a rule.
+// include/sentinel_gpu.h, the rule loaders and the per-batch launch pipeline.
+// The rule managers (validation, de-duplication, java.util.HashSet ordering,
+// FlowRuleComparator sort) are rules.h, the compiler of the device tables is
+// compile.h.  All decisions are taken on the device, by the HIP kernels of the
+// group stage (kernels.hip) and of the decide owners (decide.hip, head.hip,
+// param.hip, pvalue.hip, aux.hip, inbound.hip, cluster.hip); nothing here
+// evaluates a rule.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,12 +26,14 @@
 
 #include "../../include/sentinel_gpu.h"
 #include "authority.h"
+#include "compile.h"
 #include "dev_types.h"
 #include "embedded.h"
 #include "launch.h"
 #include "pkeys.h"
 #include "pmap.h"  // (pm_buckets: sg_param_thread_count)
 #include "pvtab.h"
+#include "rules.h"
 
 using namespace sg;
 
@@ -47,262 +52,10 @@ int fail(int code, const std::string& msg) {
         if (_e != hipSuccess) return fail(SG_EDEVICE, std::string(#x ": ") + hipGetErrorString(_e));    \
     } while (0)
 
-// ----------------------------------------------------------------- Java helpers
-int32_t j_string_hash(const char* s) {
-    if (!s) return 0;
-    uint32_t h = 0;
-    const unsigned char* p = (const unsigned char*)s;
-    while (*p) {
-        uint32_t cp;
-        if (*p < 0x80) cp = *p++;
-        else if ((*p & 0xE0) == 0xC0 && p[1]) { cp = ((p[0] & 0x1Fu) << 6) | (p[1] & 0x3Fu); p += 2; }
-        else if ((*p & 0xF0) == 0xE0 && p[1] && p[2]) { cp = ((p[0] & 0x0Fu) << 12) | ((p[1] & 0x3Fu) << 6) | (p[2] & 0x3Fu); p += 3; }
-        else if (p[1] && p[2] && p[3]) { cp = ((p[0] & 0x07u) << 18) | ((p[1] & 0x3Fu) << 12) | ((p[2] & 0x3Fu) << 6) | (p[3] & 0x3Fu); p += 4; }
-        else cp = *p++;
-        if (cp >= 0x10000) {
-            cp -= 0x10000;
-            h = 31u * h + (0xD800u + (cp >> 10));
-            h = 31u * h + (0xDC00u + (cp & 0x3FFu));
-        } else {
-            h = 31u * h + cp;
-        }
-    }
-    return (int32_t)h;
-}
-inline int32_t h31(int32_t h, int32_t v) { return (int32_t)(31u * (uint32_t)h + (uint32_t)v); }
-int32_t j_double_hash(double d) {
-    uint64_t u;
-    std::memcpy(&u, &d, 8);
-    if (d != d) u = 0x7ff8000000000000ULL;
-    return (int32_t)(uint32_t)(u ^ (u >> 32));
-}
-uint64_t dbl_bits(double d) {
-    uint64_t u;
-    std::memcpy(&u, &d, 8);
-    if (d != d) u = 0x7ff8000000000000ULL;
-    return u;
-}
-int32_t long_hash(int64_t v) { return (int32_t)(uint32_t)((uint64_t)v ^ ((uint64_t)v >> 32)); }
-bool blank(const char* s) {
-    if (!s) return true;
-    for (; *s; ++s)
-        if (*s != ' ' && *s != '\t' && *s != '\n' && *s != '\r' && *s != '\f' && *s != '\v') return false;
-    return true;
-}
-std::string sv(const char* s) { return s ? std::string(s) : std::string(); }
-// AbstractRule.limitAppEquals normal form: null, "" and "default" are interchangeable
-std::string la_norm(const char* s) { return (!s || !*s || std::strcmp(s, "default") == 0) ? "default" : std::string(s); }
-int32_t abstract_hash(const char* res, const char* la) {
-    int32_t h = res ? j_string_hash(res) : 0;
-    if (!(la == nullptr || !*la || std::strcmp(la, "default") == 0)) h = h31(h, j_string_hash(la));
-    return h;
-}
-int32_t cluster_hash(int64_t fid, int thr, int fb, int strat, int sc, int win, bool has_strat) {
-    int32_t h = fid ? long_hash(fid) : 0;
-    h = h31(h, thr);
-    h = h31(h, fb ? 1 : 0);
-    if (has_strat) h = h31(h, strat);
-    h = h31(h, sc);
-    h = h31(h, win);
-    return h;
-}
-
-// java.util.HashSet iteration order of elements inserted in `order` (see oracle Q11 note):
-// bucket index (h ^ h>>>16) & (cap-1) ascending, insertion order inside a bucket.
-void hashset_order(const std::vector<int32_t>& hashes, std::vector<int>& order) {
-    size_t n = order.size();
-    if (n <= 1) return;
-    int cap = 16;
-    for (;;) {
-        bool grown = false;
-        std::vector<int> bin(cap, 0);
-        size_t size = 0;
-        for (size_t k = 0; k < n; ++k) {
-            uint32_t h = (uint32_t)hashes[order[k]];
-            h ^= h >> 16;
-            int b = (int)(h & (uint32_t)(cap - 1));
-            if (bin[b] >= 8 && cap < 64) { cap *= 2; grown = true; break; }
-            bin[b]++;
-            if (++size > (size_t)cap * 3 / 4 && k + 1 < n) { cap *= 2; grown = true; break; }
-        }
-        if (!grown) break;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        uint32_t ha = (uint32_t)hashes[a], hb = (uint32_t)hashes[b];
-        ha ^= ha >> 16; hb ^= hb >> 16;
-        return (ha & (uint32_t)(cap - 1)) < (hb & (uint32_t)(cap - 1));
-    });
-}
-
 // ---- param value keys (ParamFlowRuleUtil.parseItemValue typing, ParamFlowRuleUtil.java:85-121)
 uint64_t mix64(uint64_t x) { return pk::mix64(x); }
 // the pure key of a value (sg_param_key): typing and hashing are pkeys.h's, which the dictionary shares
 uint64_t param_key(const char* v, const char* t) { return pk::pure_key<pk::StdHash>(v, t); }
-
-// ----------------------------------------------------------------- rule records
-struct FlowR {
-    sg_flow_rule r;
-    std::string res, la, ref;
-    int32_t hash;
-    std::string eqkey;  // FlowRule.equals
-};
-struct DegR {
-    sg_degrade_rule r;
-    std::string res, la;
-    int32_t hash;
-    std::string eqkey;
-};
-struct ParamItemR {
-    std::string obj, ct;
-    bool has_obj, has_ct;
-    int32_t count, has_count;
-};
-struct ParamR {
-    sg_param_rule r;
-    std::string res, la;
-    std::vector<ParamItemR> items;
-    std::vector<std::pair<uint64_t, int32_t>> hot;
-    int32_t hash;
-    std::string eqkey;
-};
-
-std::string flow_eqkey(const sg_flow_rule& r) {
-    char buf[512];
-    bool cc = r.cluster_mode || r.cluster_flow_id;
-    std::snprintf(buf, sizeof(buf), "%d|%016llx|%d|%d|%d|%d|%d|", r.grade, (unsigned long long)dbl_bits(r.count),
-                  r.strategy, r.control_behavior, r.warm_up_period_sec, r.max_queueing_time_ms, r.cluster_mode ? 1 : 0);
-    std::string k = std::string(buf) + sv(r.resource) + "\x01" + la_norm(r.limit_app) + "\x01" +
-                    (r.ref_resource ? "1" + std::string(r.ref_resource) : "0") + "\x01";
-    if (cc) {
-        std::snprintf(buf, sizeof(buf), "C%lld|%d|%d|%d|%d|%d", (long long)r.cluster_flow_id, r.cluster_threshold_type,
-                      r.cluster_fallback_to_local ? 1 : 0, r.cluster_strategy, r.cluster_sample_count,
-                      r.cluster_window_interval_ms);
-        k += buf;
-    }
-    return k;
-}
-int32_t flow_hash(const sg_flow_rule& r) {
-    int32_t h = abstract_hash(r.resource, r.limit_app && !blank(r.limit_app) ? r.limit_app : "default");
-    h = h31(h, r.grade);
-    h = h31(h, j_double_hash(r.count));
-    h = h31(h, r.strategy);
-    h = h31(h, r.ref_resource ? j_string_hash(r.ref_resource) : 0);
-    h = h31(h, r.control_behavior);
-    h = h31(h, r.warm_up_period_sec);
-    h = h31(h, r.max_queueing_time_ms);
-    h = h31(h, r.cluster_mode ? 1 : 0);
-    int32_t ch = 0;
-    if (r.cluster_mode || r.cluster_flow_id)
-        ch = cluster_hash(r.cluster_flow_id, r.cluster_threshold_type, r.cluster_fallback_to_local, r.cluster_strategy,
-                          r.cluster_sample_count, r.cluster_window_interval_ms, true);
-    return h31(h, ch);
-}
-bool flow_valid(const sg_flow_rule& r) { // FlowRuleUtil.isValidRule (FlowRuleUtil.java:174-228)
-    if (blank(r.resource) || !(r.count >= 0) || r.grade < 0 || r.strategy < 0 || r.control_behavior < 0) return false;
-    if (r.cluster_mode) {
-        if (r.cluster_flow_id <= 0) return false;
-        if (!(r.cluster_sample_count > 0 && r.cluster_window_interval_ms > 0 &&
-              r.cluster_window_interval_ms % r.cluster_sample_count == 0))
-            return false;
-        if (r.strategy != 0) return false;
-    }
-    if ((r.strategy == SG_STRATEGY_RELATE || r.strategy == SG_STRATEGY_CHAIN) && blank(r.ref_resource)) return false;
-    switch (r.control_behavior) {
-    case SG_CONTROL_BEHAVIOR_WARM_UP: return r.warm_up_period_sec > 0;
-    case SG_CONTROL_BEHAVIOR_RATE_LIMITER: return r.max_queueing_time_ms > 0;
-    case SG_CONTROL_BEHAVIOR_WARM_UP_RATE_LIMITER: return r.warm_up_period_sec > 0 && r.max_queueing_time_ms > 0;
-    default: return true;
-    }
-}
-std::string deg_eqkey(const sg_degrade_rule& r, int uniq) {
-    char buf[256];
-    // DegradeRule.equals compares count with != (NaN never equal): give NaN rules a unique key
-    if (r.count != r.count) std::snprintf(buf, sizeof(buf), "NaN#%d|", uniq);
-    else std::snprintf(buf, sizeof(buf), "%.17g|%d|%d|", r.count == 0 ? 0.0 : r.count, r.time_window, r.grade);
-    return std::string(buf) + sv(r.resource) + "\x01" + la_norm(r.limit_app);
-}
-int32_t deg_hash(const sg_degrade_rule& r) {
-    int32_t h = abstract_hash(r.resource, r.limit_app && !blank(r.limit_app) ? r.limit_app : "default");
-    h = h31(h, j_double_hash(r.count));
-    h = h31(h, r.time_window);
-    return h31(h, r.grade);
-}
-bool param_valid(const sg_param_rule& r) { // ParamFlowRuleUtil.isValidRule (ParamFlowRuleUtil.java:32-55)
-    if (blank(r.resource) || !(r.count >= 0) || r.grade < 0 || !r.has_param_idx || r.burst_count < 0 ||
-        r.control_behavior < 0 || r.duration_in_sec <= 0 || r.max_queueing_time_ms < 0)
-        return false;
-    if (r.cluster_mode) {
-        if (!(r.cluster_sample_count > 0 && r.cluster_window_interval_ms > 0 &&
-              r.cluster_window_interval_ms % r.cluster_sample_count == 0))
-            return false;
-        if (r.cluster_flow_id <= 0) return false;
-    }
-    return true;
-}
-// key: the hot items' keys (the engine's dictionary: two items whose pure keys collide keep their own counts)
-ParamR make_param(const sg_param_rule& s, const std::function<uint64_t(const char*, const char*)>& key) {
-    ParamR p;
-    p.r = s;
-    p.res = sv(s.resource);
-    p.la = la_norm(s.limit_app);
-    for (int i = 0; i < s.n_items; ++i) {
-        const sg_param_item& it = s.items[i];
-        ParamItemR q;
-        q.has_obj = it.object != nullptr;
-        q.obj = sv(it.object);
-        q.has_ct = it.class_type != nullptr;
-        q.ct = sv(it.class_type);
-        q.count = it.count;
-        q.has_count = it.has_count;
-        p.items.push_back(q);
-        // ParamFlowRuleUtil.parseHotItems (ParamFlowRuleUtil.java:62-83)
-        if (!it.object || !it.has_count || it.count < 0) continue;
-        uint64_t k = key(it.object, it.class_type);
-        bool found = false;
-        for (auto& h : p.hot) if (h.first == k) { h.second = it.count; found = true; }
-        if (!found) p.hot.push_back({k, it.count});
-    }
-    // ParamFlowRule.hashCode (ParamFlowRule.java:218-234)
-    int32_t h = abstract_hash(s.resource, s.limit_app && !blank(s.limit_app) ? s.limit_app : "default");
-    h = h31(h, s.grade);
-    h = h31(h, s.has_param_idx ? s.param_idx : 0);
-    h = h31(h, j_double_hash(s.count));
-    h = h31(h, s.control_behavior);
-    h = h31(h, s.max_queueing_time_ms);
-    h = h31(h, s.burst_count);
-    h = h31(h, long_hash(s.duration_in_sec));
-    int32_t lh = 1;
-    for (auto& q : p.items) {
-        int32_t e = q.has_obj ? j_string_hash(q.obj.c_str()) : 0;
-        e = h31(e, q.has_count ? q.count : 0);
-        e = h31(e, q.has_ct ? j_string_hash(q.ct.c_str()) : 0);
-        lh = h31(lh, e);
-    }
-    h = h31(h, lh);
-    h = h31(h, s.cluster_mode ? 1 : 0);
-    int32_t ch = 0;
-    if (s.cluster_mode || s.cluster_flow_id)
-        ch = cluster_hash(s.cluster_flow_id, s.cluster_threshold_type, s.cluster_fallback_to_local, 0,
-                          s.cluster_sample_count, s.cluster_window_interval_ms, false);
-    p.hash = h31(h, ch);
-    // ParamFlowRule.equals
-    char buf[512];
-    std::snprintf(buf, sizeof(buf), "%d|%016llx|%d|%d|%d|%lld|%d|%d:%d|", s.grade, (unsigned long long)dbl_bits(s.count),
-                  s.control_behavior, s.max_queueing_time_ms, s.burst_count, (long long)s.duration_in_sec,
-                  s.cluster_mode ? 1 : 0, s.has_param_idx, s.has_param_idx ? s.param_idx : 0);
-    std::string k = std::string(buf) + p.res + "\x01" + p.la + "\x01";
-    for (auto& q : p.items) {
-        std::snprintf(buf, sizeof(buf), "[%d%d%d:%d]", q.has_obj, q.has_ct, q.has_count, q.has_count ? q.count : 0);
-        k += buf + q.obj + "\x02" + q.ct + "\x03";
-    }
-    if (s.cluster_mode || s.cluster_flow_id) {
-        std::snprintf(buf, sizeof(buf), "C%lld|%d|%d|%d|%d", (long long)s.cluster_flow_id, s.cluster_threshold_type,
-                      s.cluster_fallback_to_local ? 1 : 0, s.cluster_sample_count, s.cluster_window_interval_ms);
-        k += buf;
-    }
-    p.eqkey = k;
-    return p;
-}
 
 template <class T> void dfree(T*& p) {
     if (p) (void)hipFree(p);
@@ -838,51 +591,16 @@ static void drain_hold(sg_engine* e) {
     if (rc) { e->held_rc = rc; e->held_msg = g_err; }
 }
 
-
-// CacheMap capacity of a rule's time/token maps (ParameterMetric.initialize, ParameterMetric.java:87-104)
-static uint32_t rule_map_cap(int64_t duration_sec) {
-    const int64_t c = (int64_t)PM_BASE_CAP * std::max<int64_t>(duration_sec, 1);
-    return (uint32_t)std::min<int64_t>(c, PM_TOTAL_CAP);
+// what the rule compiler (compile.h) reads of the engine
+static CompileEnv compile_env(const sg_engine* e) {
+    return CompileEnv{e->names, e->ids, e->origin_ids, e->context_ids, e->tm_base, e->pmap_index, e->psid_of, e->tmaps,
+                      e->cfg.max_resources, e->cfg.max_rules, e->cfg.cold_factor,
+                      e->mix_on, e->mix_pq, e->pv_on, e->pv_pq, e->emb_on};
 }
 
-// Embedded token server: the supported shape of a cluster flow rule, in one place for the refusals (emb_refuse) and
-// the compile (upload_rules marks XF_EMB exactly where emb_why finds nothing to object to).  A resource holding a
-// cluster-mode flow rule must have that rule as its only flow rule -- QPS grade (flow_valid has dropped a rule without
-// a flowId), limitApp "default", strategy DIRECT, a flowId no other loaded flow rule uses -- no param rules, and no
-// RELATE rule of another resource may name it: then the batch's requests depend on no verdict the batch still has to
-// find.  A rule with cluster_fallback_to_local is outside it too: the local check of a refused request is not built.
-struct EmbShape {
-    std::unordered_map<long long, int> uses;  // flowId -> cluster flow rules naming it
-    std::set<std::string> related;            // resources of a STRATEGY_RELATE pair
-    explicit EmbShape(const std::vector<FlowR>& flows) {
-        for (const FlowR& f : flows) {
-            if (f.r.cluster_mode) ++uses[(long long)f.r.cluster_flow_id];
-            if (f.r.strategy == SG_STRATEGY_RELATE && !f.ref.empty() && f.ref != f.res) { related.insert(f.ref); related.insert(f.res); }
-        }
-    }
-    // why the cluster rule f of resource r lies outside the shape (null: it is eligible)
-    const char* why(const FlowR& f, size_t r, const std::vector<std::vector<int>>& res_flow,
-                    const std::vector<std::vector<int>>& res_par) const {
-        if (r >= res_flow.size() || res_flow[r].size() != 1) return "it is not the only flow rule of its resource";
-        if (f.r.grade != SG_FLOW_GRADE_QPS) return "it is not QPS grade";
-        if (f.la != "default") return "its limitApp is not \"default\"";
-        if (f.r.strategy != SG_STRATEGY_DIRECT) return "its strategy is not DIRECT";
-        auto it = uses.find((long long)f.r.cluster_flow_id);
-        if (it == uses.end() || it->second != 1) return "another flow rule uses its flowId";
-        if (r < res_par.size() && !res_par[r].empty()) return "its resource has param rules";
-        if (related.count(f.res)) return "its resource is in a STRATEGY_RELATE component";
-        if (f.r.cluster_fallback_to_local) return "cluster_fallback_to_local is not decided in embedded mode";
-        return nullptr;
-    }
-};
-
-// Build the device rule program of every resource from the compiled host lists.
+// Compile the host lists (compile.h) and put the tables on the device.
 int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool reset_par_state) {
     uint32_t R = e->cfg.max_resources;
-    std::vector<Prog> prog(R);
-    std::vector<DRule> rules;
-    std::vector<RState> rst;
-    std::vector<DHot> hot;
     // previous rule states to carry over when a kind was not reloaded
     std::vector<RState> old_rst;
     std::vector<Prog> old_prog;
@@ -892,267 +610,14 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
         HIPCHK(hipMemcpy(old_rst.data(), e->d_rstate, e->n_dev_rules * sizeof(RState), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(old_prog.data(), e->d_prog, R * sizeof(Prog), hipMemcpyDeviceToHost));
     }
-    size_t nres = e->names.size();
-    bool any_mix = false, any_head = false;
-    std::vector<std::pair<uint32_t, int64_t>> emb_res;  // embedded mode: the XF_EMB resources and their flowIds
-    const EmbShape emb_shape(e->flows);                 // ... told by the shape test the refusals use
-    std::vector<std::pair<uint32_t, uint32_t>> relate;  // (resource, referenced resource) of RELATE rules
-    for (size_t r = 0; r < nres && r < R; ++r) {
-        Prog p;
-        std::memset(&p, 0, sizeof(p));
-        p.rule_off = (uint32_t)rules.size();
-        p.tm_base = r < e->tm_base.size() ? e->tm_base[r] : NO_ID;
-        // param rules: HashSet order (ParamFlowSlot.checkFlow iterates them, ParamFlowSlot.java:84-100)
-        const auto& pl = r < e->res_par.size() ? e->res_par[r] : std::vector<int>();
-        for (size_t i = 0; i < pl.size(); ++i) {
-            const ParamR& q = e->params[pl[i]];
-            DRule d;
-            std::memset(&d, 0, sizeof(d));
-            d.kind = RK_PARAM;
-            d.grade = (uint8_t)q.r.grade;
-            d.behavior = (uint8_t)q.r.control_behavior;
-            // cluster mode + QPS without fallback: passClusterCheck finds no TokenService in this process and
-            // passes -- the rule's metric is still initialised (ParamFlowSlot.initHotParamMetricsFor)
-            if (q.r.cluster_mode && q.r.grade == SG_FLOW_GRADE_QPS && !q.r.cluster_fallback_to_local) {
-                d.behavior = PB_INIT_ONLY;
-                // a run of such rules with fixed indices is one pseudo-rule: the set of maps it initialises
-                if (q.r.param_idx >= 0 && p.n_param && rules.back().behavior == PB_INIT_ONLY &&
-                    rules.back().param_idx >= 0) {
-                    if (q.r.param_idx < SG_MAX_ARGS) rules.back().burst |= (int32_t)(1u << q.r.param_idx);
-                    continue;
-                }
-            }
-            d.slot = (uint8_t)i;
-            d.max_queue = q.r.max_queueing_time_ms;
-            d.count = q.r.count;
-            d.burst = q.r.burst_count;
-            if (d.behavior == PB_INIT_ONLY && q.r.param_idx >= 0)  // the pseudo-rule's map set
-                d.burst = q.r.param_idx < SG_MAX_ARGS ? (int32_t)(1u << q.r.param_idx) : 0;
-            double c = q.r.count;
-            d.token_count = (c != c) ? 0 : c >= 2147483647.0 ? INT32_MAX : (int32_t)c;
-            d.token_count_l = (c != c) ? 0 : c >= 9.2e18 ? INT64_MAX : (int64_t)c;
-            d.duration_sec = q.r.duration_in_sec;
-            d.hot_off = (uint32_t)hot.size();
-            d.hot_n = (uint32_t)q.hot.size();
-            for (auto& h : q.hot) hot.push_back(DHot{h.first, h.second, 0});
-            d.pmap = e->pmap_index.at(e->psid_of.at(q.res + std::string("\0", 1) + q.eqkey));
-            d.param_idx = q.r.param_idx;
-            d.ref = NO_REF;
-            rules.push_back(d);
-            rst.push_back(RState{0, 0, 0, 0});  // a: paramIdx resolved by applyRealParamIdx + 1 (0 = not yet)
-            p.n_param++;
-        }
-        // flow rules: FlowRuleComparator order; limitApp and strategy pick the node each rule checks
-        // (FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:90-124)
-        const auto& fl = r < e->res_flow.size() ? e->res_flow[r] : std::vector<int>();
-        // FlowRuleManager.isOtherOrigin reads every rule of the resource, the cluster-only ones included
-        std::vector<uint32_t> skipped_origins;
-        for (size_t i = 0; i < fl.size(); ++i) {
-            const FlowR& f = e->flows[fl[i]];
-            if (!(f.r.cluster_mode && !f.r.cluster_fallback_to_local) || f.la == "default" || f.la == "other") continue;
-            auto oi = e->origin_ids.find(f.la);
-            if (oi != e->origin_ids.end()) skipped_origins.push_back(oi->second);
-        }
-        for (size_t i = 0; i < fl.size(); ++i) {
-            const FlowR& f = e->flows[fl[i]];
-            if (f.r.cluster_mode && !f.r.cluster_fallback_to_local) continue; // no TokenService -> pass
-            DRule d;
-            std::memset(&d, 0, sizeof(d));
-            d.kind = RK_FLOW;
-            d.grade = (uint8_t)f.r.grade;
-            d.behavior = (uint8_t)(f.r.grade == SG_FLOW_GRADE_QPS ? f.r.control_behavior : SG_CONTROL_BEHAVIOR_DEFAULT);
-            if (d.behavior > 3) d.behavior = SG_CONTROL_BEHAVIOR_DEFAULT;
-            d.slot = (uint8_t)i;
-            d.max_queue = f.r.max_queueing_time_ms;
-            d.count = f.r.count;
-            d.ref = NO_REF;
-            d.la_kind = f.la == "default" ? LA_DEFAULT : f.la == "other" ? LA_OTHER : LA_ORIGIN;
-            auto oi = e->origin_ids.find(f.la);
-            d.la_origin = oi == e->origin_ids.end() ? NO_ID : oi->second;
-            if (d.la_kind == LA_OTHER && !skipped_origins.empty()) {
-                d.hot_off = (uint32_t)hot.size();
-                d.hot_n = (uint32_t)skipped_origins.size();
-                for (uint32_t o : skipped_origins) hot.push_back(DHot{o, 0, 0});
-            }
-            d.strategy = (uint32_t)f.r.strategy;
-            d.chain_ctx = NO_ID;
-            if (f.r.strategy == SG_STRATEGY_RELATE) {  // another resource's ClusterNode (same node if itself)
-                auto it = e->ids.find(f.ref);
-                const uint32_t b = it == e->ids.end() ? NO_REF : it->second;
-                if (b != NO_REF && b != (uint32_t)r && b < R) { d.ref = b; relate.emplace_back((uint32_t)r, b); }
-            } else if (f.r.strategy == SG_STRATEGY_CHAIN) {  // the DefaultNode of the context named refResource
-                if (f.ref == "sentinel_default_context") d.chain_ctx = 0;
-                else {
-                    auto ci = e->context_ids.find(f.ref);
-                    if (ci != e->context_ids.end()) d.chain_ctx = ci->second;
-                }
-                p.multi |= PX_CHAIN;
-            }
-            if (d.la_kind != LA_DEFAULT && f.r.strategy == SG_STRATEGY_DIRECT) p.multi |= PX_ORIGIN;
-            if (d.la_kind != LA_DEFAULT || f.r.strategy == SG_STRATEGY_CHAIN || f.r.strategy > SG_STRATEGY_CHAIN)
-                p.pflags |= PF_SERIAL;  // node selection beyond the ClusterNode: the per-lane kernel
-            if (d.behavior == SG_CONTROL_BEHAVIOR_WARM_UP || d.behavior == SG_CONTROL_BEHAVIOR_WARM_UP_RATE_LIMITER) {
-                // WarmUpController.construct (WarmUpController.java:100-117)
-                int cold = e->cfg.cold_factor;
-                double c = f.r.count;
-                auto d2i = [](double v) -> int32_t {
-                    if (v != v) return 0;
-                    if (v >= 2147483647.0) return INT32_MAX;
-                    if (v <= -2147483648.0) return INT32_MIN;
-                    return (int32_t)v;
-                };
-                int32_t wt = d2i(f.r.warm_up_period_sec * c) / (cold - 1);
-                int32_t mt = (int32_t)((uint32_t)wt + (uint32_t)d2i((double)(2 * f.r.warm_up_period_sec) * c / (1.0 + cold)));
-                d.warning_token = wt;
-                d.max_token = mt;
-                d.slope = (cold - 1.0) / c / (double)(mt - wt);
-                d.count_div_cold = d2i(c) / cold;
-                p.pflags |= PF_WARM;
-            }
-            rules.push_back(d);
-            rst.push_back(RState{0, 0, -1, 0});
-            p.n_flow++;
-        }
-        const auto& dl = r < e->res_deg.size() ? e->res_deg[r] : std::vector<int>();
-        for (size_t i = 0; i < dl.size(); ++i) {
-            const DegR& g = e->degs[dl[i]];
-            DRule d;
-            std::memset(&d, 0, sizeof(d));
-            d.kind = RK_DEGRADE;
-            d.grade = (uint8_t)g.r.grade;
-            d.slot = (uint8_t)i;
-            d.count = g.r.count;
-            d.time_window = g.r.time_window;
-            if (g.r.grade == SG_DEGRADE_GRADE_EXCEPTION_COUNT) p.pflags |= PF_EXC_COUNT;
-            if (g.r.grade == SG_DEGRADE_GRADE_RT) p.pflags |= PF_RT;
-            rules.push_back(d);
-            rst.push_back(RState{0, 0, 0, 0});
-            p.n_degrade++;
-        }
-        if ((int)p.n_param + p.n_flow + p.n_degrade > 16)
-            return fail(SG_ENOTSUP, "more than 16 rules on one resource: " + e->names[r]);
-        {  // limits of the cooperative decide kernels (decide.hip JMAX_*); else one lane decides it
-            int n_rl = 0;
-            for (int i = 0; i < p.n_flow; ++i) {
-                uint8_t b = rules[p.rule_off + p.n_param + i].behavior;
-                if (b == SG_CONTROL_BEHAVIOR_RATE_LIMITER || b == SG_CONTROL_BEHAVIOR_WARM_UP_RATE_LIMITER) ++n_rl;
-            }
-            if (n_rl) p.pflags |= PF_RL;
-            // param rules beside flow / degrade rules (XF_MIX): QPS DefaultController-style token buckets on
-            // paramIdx 0 with LDS-sized maps only -- their verdicts are then a function of earlier checks of the
-            // same (rule, value) alone (no THREAD grade: its count moves with full-chain passes; no throttle:
-            // its wait would add to the flow stages')
-            bool mix = p.n_param >= 1 && p.n_param <= 4 && ((p.n_flow + p.n_degrade) > 0 || e->mix_pq) && !p.multi;
-            for (int i = 0; i < p.n_param && mix; ++i) {
-                const DRule& d = rules[p.rule_off + i];
-                if (d.param_idx < 0) mix = false;
-                else if (d.behavior == PB_INIT_ONLY) { if (d.burst & ~1) mix = false; }
-                else if (d.param_idx != 0 || d.grade != SG_FLOW_GRADE_QPS ||
-                         d.behavior != SG_CONTROL_BEHAVIOR_DEFAULT || rule_map_cap(d.duration_sec) > PQ_MAX_CAP)
-                    mix = false;
-            }
-            if (mix) {  // a thread-count map of another index is k_lane's
-                auto it = e->tmaps.lower_bound(((uint64_t)r << 8) | 1);
-                if (it != e->tmaps.end() && (*it >> 8) == (uint64_t)r) mix = false;
-            }
-            if (mix && e->mix_on) { p.xf |= XF_MIX; any_mix = true; }
-            if ((p.xf & XF_MIX) && p.n_param == 1 && rules[p.rule_off].behavior != PB_INIT_ONLY) p.xf |= XF_PLITE;
-            if ((p.n_param && !(p.xf & XF_MIX)) || p.n_flow > 4 || p.n_degrade > 4 || n_rl > 2 || p.multi)
-                p.pflags |= PF_SERIAL;
-            bool all_default_qps = true;
-            for (int i = 0; i < p.n_flow; ++i) {
-                const DRule& d = rules[p.rule_off + p.n_param + i];
-                if (d.behavior != SG_CONTROL_BEHAVIOR_DEFAULT || d.grade != SG_FLOW_GRADE_QPS) all_default_qps = false;
-            }
-            if (all_default_qps) p.pflags |= PF_FROZEN;
-            // k_pq (param.hip): param rules with a fixed paramIdx and LDS-sized rings, nothing else; QPS-grade
-            // rules, and at most one THREAD-grade rule on paramIdx 0 checked last (its check and the entry's
-            // thread-count increment are one access of the thread-count map)
-            bool pq = p.n_param >= 1 && p.n_param <= 4 && p.n_flow == 0 && p.n_degrade == 0 && !p.multi;
-            int last_checked = -1, n_thread = 0, thread_at = -1;
-            for (int i = 0; i < p.n_param && pq; ++i) {
-                const DRule& d = rules[p.rule_off + i];
-                if (d.param_idx < 0) pq = false;
-                else if (d.behavior == PB_INIT_ONLY) { if (d.burst & ~1) pq = false; }  // maps on other indices
-                else if (d.param_idx != 0) pq = false;  // sg_submit_ex args beyond [0] are k_lane's
-                else if (d.grade == SG_FLOW_GRADE_THREAD) { ++n_thread; thread_at = i; last_checked = i; }
-                else if (d.grade != SG_FLOW_GRADE_QPS || rule_map_cap(d.duration_sec) > PQ_MAX_CAP) pq = false;
-                else last_checked = i;
-            }
-            if (n_thread > 1 || (n_thread == 1 && thread_at != last_checked)) pq = false;
-            if (n_thread) p.xf |= XF_PTHREAD;
-            // a thread-count map of another index (an earlier rule set's, kept with the metric) is k_lane's too
-            if (pq) {
-                auto it = e->tmaps.lower_bound(((uint64_t)r << 8) | 1);
-                if (it != e->tmaps.end() && (*it >> 8) == (uint64_t)r) pq = false;
-            }
-            if (pq && !(p.xf & XF_MIX)) p.pflags |= PF_PQ;
-            // one checked QPS rule (DefaultController or throttle), no THREAD grade: the value-parallel passes
-            if ((p.pflags & PF_PQ) && e->pv_pq && e->pv_on && p.n_param == 1 && n_thread == 0 &&
-                rules[p.rule_off].behavior != PB_INIT_ONLY) {
-                p.xf |= XF_PVPQ;
-                any_mix = true;
-            }
-            if (p.n_flow <= 2 && p.n_degrade <= 2 && n_rl == 0) p.pflags |= PF_J16;
-            // one flow rule and nothing else on the ClusterNode: a THREAD-grade DefaultController or a QPS
-            // RateLimiter head is decided by the event-driven head owner (head.hip k_head)
-            if (p.n_param == 0 && p.n_flow == 1 && p.n_degrade == 0 && !p.multi && !(p.pflags & PF_SERIAL)) {
-                const DRule& d = rules[p.rule_off];
-                if (d.strategy == SG_STRATEGY_DIRECT && d.la_kind == LA_DEFAULT) {
-                    if (d.grade == SG_FLOW_GRADE_THREAD && d.behavior == SG_CONTROL_BEHAVIOR_DEFAULT) p.xf |= XF_HEADT;
-                    else if (d.grade == SG_FLOW_GRADE_QPS && (d.behavior == SG_CONTROL_BEHAVIOR_RATE_LIMITER ||
-                                                              (d.behavior == SG_CONTROL_BEHAVIOR_WARM_UP_RATE_LIMITER && d.count > 0)))
-                        p.xf |= XF_HEADR;
-                }
-                if (p.xf & (XF_HEADT | XF_HEADR)) any_head = true;
-            }
-        }
-        // Embedded token server: the resource's only flow rule is a cluster rule this engine counts the tokens of
-        // (emb_refuse has refused every other shape while the mode is on).  The program is what the rule compiles to
-        // without a TokenService -- no flow stage, the breakers as usual -- plus the flag: the batch's token call
-        // decides the rule (decide_enqueue)
-        if (e->emb_on && fl.size() == 1 && p.n_flow == 0) {
-            const FlowR& f = e->flows[fl[0]];
-            if (f.r.cluster_mode && !emb_shape.why(f, r, e->res_flow, e->res_par)) {
-                p.xf |= XF_EMB;
-                emb_res.emplace_back((uint32_t)r, (int64_t)f.r.cluster_flow_id);
-            }
-        }
-        // carry controller / breaker state of kinds that were not reloaded
-        if (!old_rst.empty()) {
-            const Prog& op = old_prog[r];
-            if (!reset_par_state && op.n_param == p.n_param)
-                for (int i = 0; i < p.n_param; ++i) rst[p.rule_off + i] = old_rst[op.rule_off + i];
-            if (!reset_flow_state && op.n_flow == p.n_flow)
-                for (int i = 0; i < p.n_flow; ++i) rst[p.rule_off + p.n_param + i] = old_rst[op.rule_off + op.n_param + i];
-            if (!reset_deg_state && op.n_degrade == p.n_degrade)
-                for (int i = 0; i < p.n_degrade; ++i)
-                    rst[p.rule_off + p.n_param + p.n_flow + i] = old_rst[op.rule_off + op.n_param + op.n_flow + i];
-        }
-        prog[r] = p;
-    }
-    // STRATEGY_RELATE components (co-locate the rule graph's connected components):
-    // union-find over the references; every member sorts under the representative, one segment
-    std::vector<uint32_t> comp;
-    bool any_multi = false;
-    if (!relate.empty()) {
-        comp.resize(R);
-        for (uint32_t x = 0; x < R; ++x) comp[x] = x;
-        std::function<uint32_t(uint32_t)> find = [&](uint32_t x) { return comp[x] == x ? x : comp[x] = find(comp[x]); };
-        for (auto& pr : relate) {
-            uint32_t a = find(pr.first), b = find(pr.second);
-            if (a != b) comp[std::max(a, b)] = std::min(a, b);
-        }
-        for (uint32_t x = 0; x < R; ++x) comp[x] = find(x);
-        std::vector<uint32_t> members;
-        for (uint32_t x = 0; x < R; ++x)
-            if (comp[x] != x) { members.push_back(x); members.push_back(comp[x]); }
-        std::sort(members.begin(), members.end());
-        members.erase(std::unique(members.begin(), members.end()), members.end());
-        for (uint32_t x : members) {
-            if (comp[x] == x) { prog[x].multi |= PX_MULTI; prog[x].pflags |= PF_SERIAL; }
-        }
-        any_multi = !members.empty();
+    Compiled C = compile_rules(RuleLists{e->params, e->res_par, e->flows, e->res_flow, e->degs, e->res_deg}, compile_env(e));
+    if (C.err) return fail(C.err, C.msg);
+    // carry controller / breaker state of kinds that were not reloaded
+    carry_state(old_prog, old_rst, C.prog, C.rst, !reset_par_state, !reset_flow_state, !reset_deg_state);
+    const std::vector<DRule>& rules = C.rules;
+    const std::vector<DHot>& hot = C.hot;
+    const std::vector<uint32_t>& members = C.members;
+    if (!C.comp.empty()) {
         // ClusterNode existence of the members from here on: NI_TOUCHED (a chain grant means an ENTRY of
         // the resource was decided in a finished batch: no batch is in flight during a rule load)
         std::vector<NodeInfo> ni(members.size());
@@ -1193,7 +658,6 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
             }
         }
     }
-    if (rules.size() > e->cfg.max_rules) return fail(SG_ECAPACITY, "compiled rule table exceeds max_rules");
     if (rules.size() > e->rules_cap) {
         dfree(e->d_rules); dfree(e->d_rstate);
         e->rules_cap = (uint32_t)std::max<size_t>(rules.size(), 1024);
@@ -1208,74 +672,41 @@ int upload_rules(sg_engine* e, bool reset_flow_state, bool reset_deg_state, bool
     HIPCHK(hipDeviceSynchronize());
     if (!rules.empty()) {
         HIPCHK(hipMemcpy(e->d_rules, rules.data(), rules.size() * sizeof(DRule), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_rstate, rst.data(), rst.size() * sizeof(RState), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->d_rstate, C.rst.data(), C.rst.size() * sizeof(RState), hipMemcpyHostToDevice));
     }
     if (!hot.empty()) HIPCHK(hipMemcpy(e->d_hot, hot.data(), hot.size() * sizeof(DHot), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_prog, prog.data(), R * sizeof(Prog), hipMemcpyHostToDevice));
-    if (!emb_res.empty()) {  // [res] -> flowId, read for XF_EMB resources only
+    HIPCHK(hipMemcpy(e->d_prog, C.prog.data(), R * sizeof(Prog), hipMemcpyHostToDevice));
+    if (!C.emb_res.empty()) {  // [res] -> flowId, read for XF_EMB resources only
         if (!e->d_emb_flow) HIPCHK(hipMalloc(&e->d_emb_flow, (uint64_t)R * 8));
         std::vector<int64_t> flow_of(R, 0);
-        for (const auto& er : emb_res) flow_of[er.first] = er.second;
+        for (const auto& er : C.emb_res) flow_of[er.first] = er.second;
         HIPCHK(hipMemcpy(e->d_emb_flow, flow_of.data(), (uint64_t)R * 8, hipMemcpyHostToDevice));
     }
-    e->emb_n = (uint32_t)emb_res.size();
+    e->emb_n = (uint32_t)C.emb_res.size();
     e->n_dev_rules = (uint32_t)rules.size();
-    e->has_mix = any_mix;
-    e->has_head = any_head;
-    e->has_multi = any_multi;
-    if (comp.empty()) {
+    e->has_mix = C.any_mix;
+    e->has_head = C.any_head;
+    e->has_multi = C.any_multi;
+    if (C.comp.empty()) {
         dfree(e->d_comp);
     } else {
         if (!e->d_comp) HIPCHK(hipMalloc(&e->d_comp, (uint64_t)R * 4));
-        HIPCHK(hipMemcpy(e->d_comp, comp.data(), (uint64_t)R * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->d_comp, C.comp.data(), (uint64_t)R * 4, hipMemcpyHostToDevice));
     }
     return SG_OK;
 }
 
-// What upload_rules refuses for its size -- more than 16 compiled rules on one resource, more than max_rules in all --
-// told from the host lists alone.  The loaders call it with the lists they are about to publish, before they change
-// anything of the engine: a load refused for its size leaves the engine as it was.
-static int check_rule_limits(const sg_engine* e, const std::vector<ParamR>& params, const std::vector<std::vector<int>>& res_par,
-                             const std::vector<FlowR>& flows, const std::vector<std::vector<int>>& res_flow,
-                             const std::vector<std::vector<int>>& res_deg) {
-    size_t total = 0;
-    const size_t nres = std::min<size_t>(e->names.size(), e->cfg.max_resources);
-    for (size_t r = 0; r < nres; ++r) {
-        size_t n = r < res_deg.size() ? res_deg[r].size() : 0;
-        bool run = false;  // the last compiled param rule is a PB_INIT_ONLY pseudo-rule with a fixed index
-        if (r < res_par.size())
-            for (int i : res_par[r]) {
-                const sg_param_rule& q = params[i].r;
-                const bool init = q.cluster_mode && q.grade == SG_FLOW_GRADE_QPS && !q.cluster_fallback_to_local;
-                if (init && q.param_idx >= 0 && run) continue;  // joins the pseudo-rule before it
-                run = init && q.param_idx >= 0;
-                ++n;
-            }
-        if (r < res_flow.size())
-            for (int i : res_flow[r])
-                if (!(flows[i].r.cluster_mode && !flows[i].r.cluster_fallback_to_local)) ++n;
-        if (n > 16) return fail(SG_ENOTSUP, "more than 16 rules on one resource: " + e->names[r]);
-        total += n;
-    }
-    if (total > e->cfg.max_rules) return fail(SG_ECAPACITY, "compiled rule table exceeds max_rules");
-    return SG_OK;
+// The size and embedded-shape refusals of compile.h for the lists a loader is about to publish
+static int check_rule_limits(const sg_engine* e, const RuleLists& L) {
+    std::string msg;
+    const int rc = rule_limits(L, compile_env(e), msg);
+    return rc ? fail(rc, msg) : SG_OK;
 }
-
-// What the mode cannot decide, told from the host lists alone, before anything of the engine changes (SG_ENOTSUP names
-// the rule; the caller returns it and nothing has changed).
-static int emb_refuse(const sg_engine* e, const std::vector<FlowR>& flows, const std::vector<std::vector<int>>& res_flow,
-                      const std::vector<std::vector<int>>& res_par) {
-    (void)e;
-    const EmbShape shape(flows);
-    for (size_t r = 0; r < res_flow.size(); ++r)
-        for (int i : res_flow[r]) {
-            const FlowR& f = flows[i];
-            if (!f.r.cluster_mode) continue;
-            if (const char* why = shape.why(f, r, res_flow, res_par))
-                return fail(SG_ENOTSUP, "embedded token server: cluster flow rule " + std::to_string((long long)f.r.cluster_flow_id) +
-                                            " on " + f.res + " is outside the supported shape: " + why);
-        }
-    return SG_OK;
+static int check_emb_shape(const std::vector<FlowR>& flows, const std::vector<std::vector<int>>& res_flow,
+                           const std::vector<std::vector<int>>& res_par) {
+    std::string msg;
+    const int rc = emb_refuse(flows, res_flow, res_par, msg);
+    return rc ? fail(rc, msg) : SG_OK;
 }
 
 uint32_t intern(sg_engine* e, const std::string& name) {
@@ -1677,6 +1108,10 @@ static int register_rule_resource(sg_engine* e, const char* name, uint32_t* id) 
     *id = intern(e, name);
     return SG_OK;
 }
+// ... as the callback of the list builders (rules.h): false with the reason in rc
+static auto rule_resource(sg_engine* e, int& rc) {
+    return [e, &rc](const char* name, uint32_t* id) { rc = register_rule_resource(e, name, id); return rc == SG_OK; };
+}
 
 // ---- exact parameter keys (pkeys.h, keysweep.hip; the epoch rule is in the header)
 int sg_param_intern(sg_engine* e, const char* value, const char* class_type, uint64_t* out_key) {
@@ -1877,67 +1312,23 @@ static int rebuild_cluster(sg_engine* e, const sg_flow_rule* rules, uint32_t n) 
 int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint32_t* n_loaded) {
     if (!e || (n && !rules)) return fail(SG_EINVAL, "null argument");
     if (int rc = drain(e)) return rc;  // no batch in flight while the rule tables change
-    std::vector<std::string> keys(n);
-    for (uint32_t i = 0; i < n; ++i) keys[i] = flow_eqkey(rules[i]);
+    std::vector<std::string> keys = flow_keys(rules, n);
     if (e->flow_loaded && keys == e->last_flow) { // DynamicSentinelProperty.updateValue: equal -> no-op
         if (n_loaded) *n_loaded = (uint32_t)e->flows.size();
         return SG_OK;
     }
-    std::vector<FlowR> flows;
-    std::vector<std::vector<int>> per;
-    std::unordered_map<std::string, int> seen;
-    for (uint32_t i = 0; i < n; ++i) {
-        const sg_flow_rule& r = rules[i];
-        if (!flow_valid(r)) continue;
-        uint32_t rid;
-        int rc = register_rule_resource(e, r.resource, &rid);
-        if (rc) return rc;
-        if (r.strategy == SG_STRATEGY_RELATE && r.ref_resource && *r.ref_resource) {  // its ClusterNode is read
-            uint32_t ref;
-            rc = register_rule_resource(e, r.ref_resource, &ref);
-            if (rc) return rc;
-        }
-        std::string k = std::to_string(rid) + "#" + keys[i];
-        if (seen.count(k)) continue; // HashSet.add of an equal rule
-        seen[k] = 1;
-        FlowR f;
-        f.r = r;
-        f.res = r.resource;
-        f.la = la_norm(r.limit_app);
-        f.ref = sv(r.ref_resource);
-        f.hash = flow_hash(r);
-        f.eqkey = keys[i];
-        flows.push_back(f);
-        if (per.size() <= rid) per.resize(rid + 1);
-        per[rid].push_back((int)flows.size() - 1);
-    }
-    std::vector<int32_t> hs(flows.size());
-    for (size_t i = 0; i < flows.size(); ++i) hs[i] = flows[i].hash;
-    for (auto& l : per) {
-        hashset_order(hs, l);
-        // Collections.sort(rules, FlowRuleComparator) -- stable (FlowRuleComparator.java:30-55)
-        std::stable_sort(l.begin(), l.end(), [&](int a, int b) {
-            const FlowR &x = flows[a], &y = flows[b];
-            auto cmp = [](const FlowR& o1, const FlowR& o2) {
-                if (o1.r.cluster_mode && !o2.r.cluster_mode) return 1;
-                if (!o1.r.cluster_mode && o2.r.cluster_mode) return -1;
-                if (o1.la == o2.la) return 0;
-                if (o1.la == "default") return 1;
-                if (o2.la == "default") return -1;
-                return 0;
-            };
-            return cmp(x, y) < 0;
-        });
-    }
-    if (int rc = check_rule_limits(e, e->params, e->res_par, flows, per, e->res_deg)) return rc;
+    RuleList<FlowR> L;
+    int rrc = SG_OK;
+    if (!build_flow_list(rules, n, std::move(keys), rule_resource(e, rrc), L)) return rrc;
+    if (int rc = check_rule_limits(e, RuleLists{e->params, e->res_par, L.recs, L.per, e->degs, e->res_deg})) return rc;
     if (e->emb_on)
-        if (int rc = emb_refuse(e, flows, per, e->res_par)) return rc;
+        if (int rc = check_emb_shape(L.recs, L.per, e->res_par)) return rc;
     // publish
     auto old_flows = std::move(e->flows);
     auto old_per = std::move(e->res_flow);
     auto old_names = std::move(e->rule_names);
-    e->flows = std::move(flows);
-    e->res_flow = std::move(per);
+    e->flows = std::move(L.recs);
+    e->res_flow = std::move(L.per);
     resize_lists(e, e->res_flow);
     e->rule_names.clear();  // the origin / context names the flow rules read (sg_intern_* recompiles on first sight)
     for (auto& f : e->flows) {
@@ -1951,7 +1342,7 @@ int sg_load_flow_rules(sg_engine* e, const sg_flow_rule* rules, uint32_t n, uint
         e->rule_names = std::move(old_names);
         return rc;
     }
-    e->last_flow = keys;
+    e->last_flow = std::move(L.keys);
     e->flow_loaded = true;
     rc = rebuild_cluster(e, rules, n);
     if (rc) return rc;
@@ -2026,48 +1417,25 @@ int sg_load_authority_rules(sg_engine* e, const sg_authority_rule* rules, uint32
 int sg_load_degrade_rules(sg_engine* e, const sg_degrade_rule* rules, uint32_t n, uint32_t* n_loaded) {
     if (!e || (n && !rules)) return fail(SG_EINVAL, "null argument");
     if (int rc = drain(e)) return rc;  // no batch in flight while the rule tables change
-    std::vector<std::string> keys(n);
-    for (uint32_t i = 0; i < n; ++i) keys[i] = deg_eqkey(rules[i], (int)i);
+    std::vector<std::string> keys = deg_keys(rules, n);
     bool has_nan = false;
     for (uint32_t i = 0; i < n; ++i) has_nan |= rules[i].count != rules[i].count;
     if (e->deg_loaded && !has_nan && keys == e->last_deg) {
         if (n_loaded) *n_loaded = (uint32_t)e->degs.size();
         return SG_OK;
     }
-    std::vector<DegR> degs;
-    std::vector<std::vector<int>> per;
-    std::unordered_map<std::string, int> seen;
-    for (uint32_t i = 0; i < n; ++i) {
-        const sg_degrade_rule& r = rules[i];
-        if (blank(r.resource) || !(r.count >= 0) || r.time_window <= 0) continue; // isValidRule
-        uint32_t rid;
-        int rc = register_rule_resource(e, r.resource, &rid);
-        if (rc) return rc;
-        std::string k = std::to_string(rid) + "#" + keys[i];
-        if (seen.count(k)) continue;
-        seen[k] = 1;
-        DegR d;
-        d.r = r;
-        d.res = r.resource;
-        d.la = la_norm(r.limit_app);
-        d.hash = deg_hash(r);
-        d.eqkey = keys[i];
-        degs.push_back(d);
-        if (per.size() <= rid) per.resize(rid + 1);
-        per[rid].push_back((int)degs.size() - 1);
-    }
-    std::vector<int32_t> hs(degs.size());
-    for (size_t i = 0; i < degs.size(); ++i) hs[i] = degs[i].hash;
-    for (auto& l : per) hashset_order(hs, l);
-    if (int rc = check_rule_limits(e, e->params, e->res_par, e->flows, e->res_flow, per)) return rc;
+    RuleList<DegR> L;
+    int rrc = SG_OK;
+    if (!build_degrade_list(rules, n, std::move(keys), rule_resource(e, rrc), L)) return rrc;
+    if (int rc = check_rule_limits(e, RuleLists{e->params, e->res_par, e->flows, e->res_flow, L.recs, L.per})) return rc;
     auto od = std::move(e->degs);
     auto op = std::move(e->res_deg);
-    e->degs = std::move(degs);
-    e->res_deg = std::move(per);
+    e->degs = std::move(L.recs);
+    e->res_deg = std::move(L.per);
     resize_lists(e, e->res_deg);
     int rc = upload_rules(e, false, true, false);
     if (rc) { e->degs = std::move(od); e->res_deg = std::move(op); return rc; }
-    e->last_deg = keys;
+    e->last_deg = std::move(L.keys);
     e->deg_loaded = true;
     if (n_loaded) *n_loaded = (uint32_t)e->degs.size();
     return SG_OK;
@@ -2386,11 +1754,7 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
         if (entry) pins.now.push_back(k);
         return k;
     };
-    for (uint32_t i = 0; i < n; ++i) {
-        if (rules[i].n_items > 0 && !rules[i].items) return fail(SG_EINVAL, "param rule items pointer is null");
-        all.push_back(make_param(rules[i], item_key));
-        keys.push_back(all.back().eqkey);
-    }
+    if (!param_records(rules, n, item_key, all, keys)) return fail(SG_EINVAL, "param rule items pointer is null");
     // a negative paramIdx is rewritten in the loaded rule objects (ParamFlowSlot.applyRealParamIdx), so the
     // property's equality check never matches the list that created them: such a list always reloads
     bool neg = false;
@@ -2399,24 +1763,11 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
         if (n_loaded) *n_loaded = (uint32_t)e->params.size();
         return SG_OK;
     }
-    std::vector<ParamR> ps;
-    std::vector<std::vector<int>> per;
-    std::unordered_map<std::string, int> seen;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (!param_valid(rules[i])) continue;
-        uint32_t rid;
-        int rc = register_rule_resource(e, rules[i].resource, &rid);
-        if (rc) return rc;
-        std::string k = std::to_string(rid) + "#" + keys[i];
-        if (seen.count(k)) continue;
-        seen[k] = 1;
-        ps.push_back(all[i]);
-        if (per.size() <= rid) per.resize(rid + 1);
-        per[rid].push_back((int)ps.size() - 1);
-    }
-    std::vector<int32_t> hs(ps.size());
-    for (size_t i = 0; i < ps.size(); ++i) hs[i] = ps[i].hash;
-    for (auto& l : per) hashset_order(hs, l);
+    RuleList<ParamR> L;
+    int rrc = SG_OK;
+    if (!build_param_list(all, std::move(keys), rule_resource(e, rrc), L)) return rrc;
+    std::vector<ParamR>& ps = L.recs;
+    std::vector<std::vector<int>>& per = L.per;
     // ParameterMetric lifetime: resources that had rules and now have none lose their metric
     // (ParamFlowRuleManager.java:150-159); all metrics are cleared for an empty list.  Work on copies: the maps
     // are rebuilt (and may fail with SG_ECAPACITY) before anything of the engine changes.
@@ -2455,9 +1806,9 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
                 if (idx < 0 || idx == k) tmaps.insert(((uint64_t)r << 8) | (uint64_t)k);
         }
     // the checks first: with SG_ENOTSUP / SG_ECAPACITY neither the cluster rules nor the maps change
-    if (int rc = check_rule_limits(e, ps, per, e->flows, e->res_flow, e->res_deg)) return rc;
+    if (int rc = check_rule_limits(e, RuleLists{ps, per, e->flows, e->res_flow, e->degs, e->res_deg})) return rc;
     if (e->emb_on)
-        if (int rc = emb_refuse(e, e->flows, e->res_flow, per)) return rc;
+        if (int rc = check_emb_shape(e->flows, e->res_flow, per)) return rc;
     uint64_t need = (rcap.size() + tmaps.size()) * (uint64_t)PM_MIN_NB * PM_BKT;  // (new maps' first regions)
     if (need > (1ull << e->cfg.param_table_log2))
         return fail(SG_ECAPACITY, "hot-parameter maps need " + std::to_string(need) + " slots, param_table_log2 = " +
@@ -2483,7 +1834,7 @@ int sg_load_param_rules(sg_engine* e, const sg_param_rule* rules, uint32_t n, ui
         HIPCHK(hipStreamSynchronize(e->stream));
         (void)hipFree(d);
     }
-    e->last_par = keys;
+    e->last_par = std::move(L.keys);
     e->par_loaded = true;
     pins.end = 2;
     if (!e->params.empty() && !e->d_keyring) {  // thread counts can exist from now on: remember ENTRY keys
@@ -4237,7 +3588,7 @@ int sg_cluster_embedded(sg_engine* e, int32_t on) {
     const bool want = on != 0;
     if (want == e->emb_on) return SG_OK;
     if (want)
-        if (int rc = emb_refuse(e, e->flows, e->res_flow, e->res_par)) return rc;
+        if (int rc = check_emb_shape(e->flows, e->res_flow, e->res_par)) return rc;
     e->emb_on = want;
     const int rc = upload_rules(e, false, false, false);
     if (rc) {
